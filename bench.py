@@ -16,7 +16,12 @@ C++ caller uses) inside the step is reported beside it ("upload_inclusive").  Mu
 (weak scaling); the loop-closure ICP (C4: 500k vs 500k) is sharded across the
 ranks with the record all-gather (lio_gpu.dist) and reported in "loop_icp".
 
-    python bench.py --gpus N --steps K --warmup W
+A plain run does only what `value` needs: set-up, warm-up, the K timed steps, a pass over the distinct
+resident scans for the evaluation counts, the outputs if --dump-outputs is given, and the line.  Every other
+figure (upload_inclusive, roofline, cpu_baseline, loop_icp, multi_stream, pipeline, loop_sequence) is
+measured only with --full and is null in the line of a plain run.
+
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     torchrun --nproc-per-node N bench.py --gpus N ...
 """
 from __future__ import annotations
@@ -69,6 +74,13 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the secondary figures after the headline: the untimed statistics pass over "
+                         "all K steps, upload_inclusive, roofline (kernel event pass), pipeline, loop_sequence, "
+                         "multi_stream, loop_icp and the CPU baselines (each still has its own switch below)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step's lio_ieskf_update left with its "
+                         "caller as DIR/<name>.npy (float64): state, cov, stats, knn_idx, point_selected")
     ap.add_argument("--prewarm-s", type=float, default=0.5,
                     help="untimed steps for this many seconds before the --warmup steps (GPU clock ramp)")
     ap.add_argument("--config", default="C3", choices=["C1", "C2", "C3", "C5"])
@@ -414,51 +426,69 @@ def main():
     elapsed = time.perf_counter() - t_start
     gc.enable()
     t_steps = [b - a for a, b in zip(t_steps[:-1], t_steps[1:])]
-    # untimed statistics pass over the same steps (the updates are deterministic per scan): host split,
-    # evaluations per scan, pose error against the ground truth
-    h_evals = knn_calls = 0
-    capi_ms = launch_ms = wait_ms = solve_ms = 0.0
+    if args.dump_outputs and args.steps > 0:
+        # what the last timed step left with its caller: the updated state and covariance, the update's
+        # statistics, and h_share_model's globals of its last evaluation (Nearest_Points ids,
+        # point_selected_surf) — copied out before any later pass overwrites them
+        n_last = ptrs[(args.steps - 1) % len(scans)][1]
+        nn = np.empty((n_last, 5), np.int32)
+        sel = np.empty(n_last, np.uint8)
+        F.check(lib_.lio_get_knn(hm._h, nn.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), None))
+        F.check(lib_.lio_get_planes(hm._h, None, sel.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))))
+        out = {"state": np.concatenate([np.array(list(getattr(s_c, f)), np.float64) for f, _ in s_c._fields_]),
+               "cov": P_c.astype(np.float64),
+               "stats": np.array([st_c.h_evals, st_c.knn_calls, st_c.converged, st_c.n_eff, st_c.res_mean],
+                                 np.float64),
+               "knn_idx": nn.astype(np.float64), "point_selected": sel.astype(np.float64)}
+        d_out = args.dump_outputs if world == 1 else os.path.join(args.dump_outputs, f"rank{rank}")
+        os.makedirs(d_out, exist_ok=True)
+        for name, a in out.items():
+            np.save(os.path.join(d_out, name + ".npy"), a)
+    # untimed statistics pass (the updates are deterministic per scan): host split, evaluations per scan,
+    # pose error against the ground truth.  --full: over the same K steps; a plain run: one step per
+    # distinct resident scan, each counted as often as the timed loop used it
+    n_stat = args.steps if args.full else min(args.steps, len(scans))
+    per_step = []
     pos_err = []
-    for k in range(args.steps):
+    for k in range(n_stat):
         st = step(k)
-        capi_ms += st.wall_ms
-        launch_ms += st.launch_ms
-        wait_ms += st.wait_ms
-        solve_ms += st.solve_ms
-        h_evals += st.h_evals
-        knn_calls += st.knn_calls
+        per_step.append((st.wall_ms, st.launch_ms, st.wait_ms, st.solve_ms, st.h_evals, st.knn_calls))
         if k < len(scans):
             pos_err.append(float(np.linalg.norm(np.array(list(s_c.pos)) - scans[k % len(scans)].pos_gt)))
-    # the integration path a C++ caller takes: the scan is handed over in host memory
-    # and uploaded by lio_scan_set (pinned buffer -> hipMemcpyAsync on the ctx stream) inside the step.
-    # Reported beside `value`, never as it (value = inputs already resident in HBM).
-    h_scans = [torch.from_numpy(s.body).pin_memory() for s in scans]
-    lib = F._capi.lib()
-    h_ptrs = [ctypes.cast(t.data_ptr(), ctypes.POINTER(ctypes.c_float)) for t in h_scans]
+    capi_ms, launch_ms, wait_ms, solve_ms, h_evals, knn_calls = (
+        sum(per_step[k % n_stat][i] for k in range(args.steps)) for i in range(6))
+    up_s = tm = None
+    if args.full:
+        # the integration path a C++ caller takes: the scan is handed over in host memory
+        # and uploaded by lio_scan_set (pinned buffer -> hipMemcpyAsync on the ctx stream) inside the step.
+        # Reported beside `value`, never as it (value = inputs already resident in HBM).
+        h_scans = [torch.from_numpy(s.body).pin_memory() for s in scans]
+        lib = F._capi.lib()
+        h_ptrs = [ctypes.cast(t.data_ptr(), ctypes.POINTER(ctypes.c_float)) for t in h_scans]
 
-    def step_upload(k):
-        j = k % len(scans)
-        F.check(lib.lio_scan_set(hm._h, h_ptrs[j], len(scans[j].body)))
-        ctypes.pointer(s_c)[0] = init_c[j]
-        np.copyto(P_c, P0)
-        kf.update_raw(s_c, P_c, st_c)
+        def step_upload(k):
+            j = k % len(scans)
+            F.check(lib.lio_scan_set(hm._h, h_ptrs[j], len(scans[j].body)))
+            ctypes.pointer(s_c)[0] = init_c[j]
+            np.copyto(P_c, P0)
+            kf.update_raw(s_c, P_c, st_c)
 
-    for k in range(min(args.warmup, 5)):
-        step_upload(k)
-    barrier()
-    t_up = time.perf_counter()
-    for k in range(args.steps):
-        step_upload(k)
-    barrier()
-    up_s = time.perf_counter() - t_up
-    # kernel durations for the roofline: a separate pass with HIP events on the
-    # ctx stream (events cost host time, so they stay out of the timed region)
-    hm.reset_timing()
-    hm.set_timing(True)
-    for k in range(min(args.steps, 50)):
-        step(k)
-    hm.set_timing(False)
-    tm = hm.timing()
+        for k in range(min(args.warmup, 5)):
+            step_upload(k)
+        barrier()
+        t_up = time.perf_counter()
+        for k in range(args.steps):
+            step_upload(k)
+        barrier()
+        up_s = time.perf_counter() - t_up
+        # kernel durations for the roofline: a separate pass with HIP events on the
+        # ctx stream (events cost host time, so they stay out of the timed region)
+        hm.reset_timing()
+        hm.set_timing(True)
+        for k in range(min(args.steps, 50)):
+            step(k)
+        hm.set_timing(False)
+        tm = hm.timing()
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device=coll_dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -469,55 +499,57 @@ def main():
     ms_per_iter = elapsed / max(h_evals, 1) * 1e3
 
     n_pts = sp
-    knn_avg_ms = tm["knn_ms"] / max(tm["knn_launches"], 1)
-    near_avg_ms = tm["near_ms"] / max(tm["near_launches"], 1)
-    far_avg_ms = tm["far_ms"] / max(tm["far_launches"], 1)
-    reuse_avg_ms = tm["reuse_ms"] / max(tm["reuse_launches"], 1)
-    achieved = BYTES_PER_PT_KNN * n_pts / (knn_avg_ms * 1e-3) / 1e9 if tm["knn_launches"] else None
-    traffic = None
-    if os.path.exists(args.pmc):
-        try:
-            pmc = json.load(open(args.pmc))
-            if pmc.get("config") == args.config:
-                traffic = pmc.get("knn_hbm_bytes_per_launch")
-        except Exception:
-            traffic = None
-    # unit of work = one kNN h-evaluation (112 B/pt), which runs as
-    # knn_near_kernel + knn_far_kernel + plane_kernel back to back on the ctx
-    # stream; achieved = algorithmic bytes / the sum of the three kernels' own
-    # execution spans (hipExtLaunchKernel start/stop events on that stream, a
-    # separate pass after the timed loop: the spans rocprofv3 reports, no gaps)
-    # issue / wait breakdown of the evaluation's kernels from a separate SQ + GRBM counter pass on this config
-    # (profiles/, scripts/pmc_sq_summary.py: VALU busy at 2 cycles per wave64 instruction, wait = SQ_WAIT_ANY /
-    # SQ_WAVE_CYCLES, issue stall = SQ_WAIT_INST_ANY / SQ_WAVE_CYCLES)
-    sq = None
-    if args.config == "C3" and os.path.exists(args.pmc_sq):
-        try:
-            pm = json.load(open(args.pmc_sq))
-            pick = {"near_first": "knn_near_kernel<false, false", "near_seeded": "knn_near_kernel<false, true",
-                    "far": "knn_far_kernel", "plane": "plane_kernel", "reuse": "h_model_reuse_kernel"}
-            sq = {}
-            for name, pre in pick.items():
-                k = next((k for k in pm if k.startswith(pre)), None)
-                if k:
-                    sq[name] = {f: pm[k][f] for f in ("valu_busy_frac", "wait_frac", "issue_stall_frac")}
-            sq = sq or None
-        except Exception:
-            sq = None
-    roofline = {"bound": "hbm", "achieved": round(achieved, 2) if achieved else None, "peak": HBM_PEAK_GBS,
-                "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5) if achieved else None,
-                # traffic: HBM bytes per launch from a separate rocprofv3 --pmc pass (not this run)
-                "traffic": traffic,
-                "kernel": "kNN h-evaluation = knn_near_kernel + knn_far_kernel + plane_kernel",
-                "bytes_per_launch": BYTES_PER_PT_KNN * n_pts, "avg_launch_ms": round(knn_avg_ms, 5),
-                "near_kernel_avg_ms": round(near_avg_ms, 5), "far_kernel_avg_ms": round(far_avg_ms, 5),
-                "plane_kernel_avg_ms": round(tm["plane_ms"] / max(tm["plane_launches"], 1), 5),
-                "reuse_kernel_avg_ms": round(reuse_avg_ms, 5),
-                "reuse_achieved_gbs": round(BYTES_PER_PT_REUSE * n_pts / (reuse_avg_ms * 1e-3) / 1e9, 2)
-                if tm["reuse_launches"] else None,
-                # NOT measured in this run: counter passes committed under profiles/ 
-                "from_profile": {"traffic": _profile_meta(args.pmc) if traffic is not None else None,
-                                 "sq_breakdown": sq, "sq": _profile_meta(args.pmc_sq) if sq else None}}
+    roofline = None
+    if args.full:
+        knn_avg_ms = tm["knn_ms"] / max(tm["knn_launches"], 1)
+        near_avg_ms = tm["near_ms"] / max(tm["near_launches"], 1)
+        far_avg_ms = tm["far_ms"] / max(tm["far_launches"], 1)
+        reuse_avg_ms = tm["reuse_ms"] / max(tm["reuse_launches"], 1)
+        achieved = BYTES_PER_PT_KNN * n_pts / (knn_avg_ms * 1e-3) / 1e9 if tm["knn_launches"] else None
+        traffic = None
+        if os.path.exists(args.pmc):
+            try:
+                pmc = json.load(open(args.pmc))
+                if pmc.get("config") == args.config:
+                    traffic = pmc.get("knn_hbm_bytes_per_launch")
+            except Exception:
+                traffic = None
+        # unit of work = one kNN h-evaluation (112 B/pt), which runs as
+        # knn_near_kernel + knn_far_kernel + plane_kernel back to back on the ctx
+        # stream; achieved = algorithmic bytes / the sum of the three kernels' own
+        # execution spans (hipExtLaunchKernel start/stop events on that stream, a
+        # separate pass after the timed loop: the spans rocprofv3 reports, no gaps)
+        # issue / wait breakdown of the evaluation's kernels from a separate SQ + GRBM counter pass on this config
+        # (profiles/, scripts/pmc_sq_summary.py: VALU busy at 2 cycles per wave64 instruction, wait = SQ_WAIT_ANY /
+        # SQ_WAVE_CYCLES, issue stall = SQ_WAIT_INST_ANY / SQ_WAVE_CYCLES)
+        sq = None
+        if args.config == "C3" and os.path.exists(args.pmc_sq):
+            try:
+                pm = json.load(open(args.pmc_sq))
+                pick = {"near_first": "knn_near_kernel<false, false", "near_seeded": "knn_near_kernel<false, true",
+                        "far": "knn_far_kernel", "plane": "plane_kernel", "reuse": "h_model_reuse_kernel"}
+                sq = {}
+                for name, pre in pick.items():
+                    k = next((k for k in pm if k.startswith(pre)), None)
+                    if k:
+                        sq[name] = {f: pm[k][f] for f in ("valu_busy_frac", "wait_frac", "issue_stall_frac")}
+                sq = sq or None
+            except Exception:
+                sq = None
+        roofline = {"bound": "hbm", "achieved": round(achieved, 2) if achieved else None, "peak": HBM_PEAK_GBS,
+                    "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5) if achieved else None,
+                    # traffic: HBM bytes per launch from a separate rocprofv3 --pmc pass (not this run)
+                    "traffic": traffic,
+                    "kernel": "kNN h-evaluation = knn_near_kernel + knn_far_kernel + plane_kernel",
+                    "bytes_per_launch": BYTES_PER_PT_KNN * n_pts, "avg_launch_ms": round(knn_avg_ms, 5),
+                    "near_kernel_avg_ms": round(near_avg_ms, 5), "far_kernel_avg_ms": round(far_avg_ms, 5),
+                    "plane_kernel_avg_ms": round(tm["plane_ms"] / max(tm["plane_launches"], 1), 5),
+                    "reuse_kernel_avg_ms": round(reuse_avg_ms, 5),
+                    "reuse_achieved_gbs": round(BYTES_PER_PT_REUSE * n_pts / (reuse_avg_ms * 1e-3) / 1e9, 2)
+                    if tm["reuse_launches"] else None,
+                    # NOT measured in this run: counter passes committed under profiles/ 
+                    "from_profile": {"traffic": _profile_meta(args.pmc) if traffic is not None else None,
+                                     "sq_breakdown": sq, "sq": _profile_meta(args.pmc_sq) if sq else None}}
 
     line = {
         "metric": "scans/sec (100k-pt scan vs N-pt map) + ms/IESKF-iteration, 1 GPU",
@@ -547,7 +579,8 @@ def main():
                              "ms_per_step": round(up_s / args.steps * 1e3, 4),
                              "bytes_per_scan": 12 * sp,
                              "note": "scan uploaded from pinned host memory by lio_scan_set inside each step "
-                                     "(rank-local; PCIe included)"},
+                                     "(rank-local; PCIe included)"} if up_s is not None else None,
+        "full": args.full,  # False: the keys from upload_inclusive on, map_incremental apart, were not measured
         "roofline": roofline, "cpu_baseline": None, "loop_icp": None, "multi_stream": None, "map_incremental": incr,
         "pipeline": None, "loop_sequence": None,
     }
@@ -556,7 +589,7 @@ def main():
     # collective of the secondary sections (the loop ICP's RCCL exchange) never returns, so a hang there
     # cannot cost the scaling run its line
     watchdog = None
-    if dist is not None:
+    if dist is not None and args.full:
         import threading
 
         def _abandon():
@@ -571,7 +604,7 @@ def main():
 
     # ------------------------------------------------- C5 stream with its loop leg (secondary)
     pipeline = None
-    if args.pipeline > 0 and rank == 0:
+    if args.full and args.pipeline > 0 and rank == 0:
         from lio_gpu import pipeline as PL
 
         pmp, pL, psp, pkind = synth.CONFIGS["C5"]
@@ -643,7 +676,7 @@ def main():
     # prewarmed when the node starts (prewarm_ms: buffers at their floors, code objects loaded), so no call is
     # cold, and no call after the first may allocate (lio_alloc_count)
     loop_seq = None
-    if args.loop_seq > 0 and rank == 0:
+    if args.full and args.loop_seq > 0 and rank == 0:
         try:
             import tempfile
 
@@ -679,7 +712,7 @@ def main():
     # One stream is latency-bound (host round trip per h-evaluation); independent sensors / robots
     # can share the card. Each stream: its own map replica, ctx and HIP stream, one host thread.
     multi = None
-    if args.streams and rank == 0:
+    if args.full and args.streams and rank == 0:
         import threading
 
         multi = []
@@ -722,7 +755,7 @@ def main():
 
     # ------------------------------------------------------------- loop ICP (sharded)
     loop_icp = src = dst = None
-    if not args.no_icp:
+    if args.full and not args.no_icp:
         try:
             loop_icp, src, dst = _loop_icp(args, LC, synth, local, world, rank, dist, rehearse, coll_dev, barrier, torch)
         except Exception as e:  # N > 1: an exchange failure must not cost the headline line
@@ -735,7 +768,7 @@ def main():
 
     # ------------------------------------------------------------- CPU baseline
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import oracle_py as O
 

@@ -14,6 +14,6 @@ for v in "$@"; do
     if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then echo "!! rc=$rc"; exit $rc; fi
     timeout -k 10 300 python scripts/knn_timing.py C3 > "$OUT/knn_$v.log" 2>&1 || exit $?
     cat "$OUT/knn_$v.log"
-    timeout -k 10 300 python bench.py --steps 400 --warmup 20 --no-icp --no-cpu --streams '' > "$OUT/bench_$v.log" 2>&1 || exit $?
+    timeout -k 10 300 python bench.py --full --steps 400 --warmup 20 --no-icp --no-cpu --streams '' > "$OUT/bench_$v.log" 2>&1 || exit $?
     python3 -c "import json,sys;d=json.loads([l for l in open('$OUT/bench_$v.log') if l.startswith('{')][-1]);r=d['roofline'];print('value',d['value'],'ms',d['ms_per_step'],'near',r['near_kernel_avg_ms'],'far',r['far_kernel_avg_ms'],'plane',r['plane_kernel_avg_ms'],'reuse',r['reuse_kernel_avg_ms'])"
 done

@@ -7,7 +7,7 @@ mkdir -p "$OUT"
 run() {  # run <name> <env...> -- (bench args fixed)
     local name=$1; shift
     echo "== $name"
-    timeout -k 10 300 env "$@" python bench.py --steps 400 --warmup 40 --no-icp --no-cpu > "$OUT/$name.log" 2>&1
+    timeout -k 10 300 env "$@" python bench.py --full --steps 400 --warmup 40 --no-icp --no-cpu > "$OUT/$name.log" 2>&1
     local rc=$?
     grep '^{' "$OUT/$name.log" | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$name', d['value'], d['ms_per_step'], d['capi_ms_per_scan'])"
     [ $rc -eq 0 ] || { echo "rc=$rc, stopping"; exit $rc; }

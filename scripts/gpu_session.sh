@@ -37,7 +37,7 @@ for s in $STEPS; do
     pipe)  runs pytest_pipe 600 python -u -m pytest tests/test_gpu_pipeline.py -x -v -s -p no:cacheprovider --timeout 500 --timeout-method thread ;;
     icpf)  runs pytest_icpf 600 python -u -m pytest tests/test_gpu_icp.py -k "float or double" -x -v -s -p no:cacheprovider --timeout 500 --timeout-method thread ;;
     icpx)  runs pytest_icpx 600 python -u -m pytest tests/test_gpu_icp.py -k "exchange or group" -x -v -s -p no:cacheprovider --timeout 300 --timeout-method thread ;;
-    spawn2) LIO_BENCH_REHEARSE=1 run spawn2 500 python bench.py --gpus 2 --steps 50 --warmup 5 --pipeline 0 --no-cpu --streams '' --icp-reps 2 ;;
+    spawn2) LIO_BENCH_REHEARSE=1 run spawn2 500 python bench.py --full --gpus 2 --steps 50 --warmup 5 --pipeline 0 --no-cpu --streams '' --icp-reps 2 ;;
     map)   runs pytest_map 900 python -u -m pytest tests/test_gpu_map.py tests/test_gpu_fullsize.py -x -v -p no:cacheprovider --timeout 600 --timeout-method thread ;;
     shardt) runs pytest_shard 900 python -u -m pytest tests/test_gpu_icp.py tests/test_gpu_fullsize.py tests/test_gpu_dist.py -k "group or exchange or emulated or multiprocess or recovery or timeout" -x -v -s -p no:cacheprovider --timeout 600 --timeout-method thread ;;
     shardprof) run shardprof4 300 env LIO_FSH_TRACE=1 python scripts/icp_shard_profile.py 4 3 B &&
@@ -76,11 +76,11 @@ f = '/tmp/ls.bin'; PL.write_loop_sequence(f, kfs, range(12, 24))
 o = PL.run_loop_sequence(f); pc = o.pop('per_call'); print(json.dumps(o))
 for c in pc: print(c['k'], round(c['ms'], 3), round(c['submaps_ms'], 3), round(c['icp_ms'], 3), c['closest'], c['n_src'], c['n_dst'], c['iterations'], c['valid'], c['allocs'])
 " ;;
-    bench) run bench 600 python bench.py --steps 200 --warmup 20 ;;
+    bench) run bench 600 python bench.py --full --steps 200 --warmup 20 ;;
     knn)   run knn_timing 300 python scripts/knn_timing.py C2 &&
            run knn_prof 300 rocprofv3 --kernel-trace --stats -d "$OUT/knnprof" -o run --output-format csv -- python scripts/knn_timing.py C2 ;;
-    quick) run bench_quick 400 python bench.py --steps 60 --warmup 5 --icp-reps 2 --cpu-scans 10 --cpu-warmup 2 ;;
-    driver) run bench_driver 600 python bench.py --gpus 1 --steps 20 --warmup 5 ;;
+    quick) run bench_quick 400 python bench.py --full --steps 60 --warmup 5 --icp-reps 2 --cpu-scans 10 --cpu-warmup 2 ;;
+    driver) run bench_driver 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 ;;
     driverq) run bench_driverq1 300 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu --pipeline 0 --streams '' --no-icp &&
              run bench_driverq2 300 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu --pipeline 0 --streams '' --no-icp &&
              run bench_driverq3 300 python bench.py --gpus 1 --steps 50 --warmup 5 --no-cpu --pipeline 0 --streams '' --no-icp ;;
@@ -90,7 +90,7 @@ for c in pc: print(c['k'], round(c['ms'], 3), round(c['submaps_ms'], 3), round(c
     setup) run icp_setup 300 python scripts/icp_setup_timing.py &&
            run icp_setup2 300 python scripts/icp_setup_timing.py ;;
     msab)  echo "msab: the round-2 build it compared against is no longer kept (result: profiles/r04_multi_stream_ab.txt)" ;;
-    pmcsq) run pmcsq_c3 300 timeout -s KILL 200 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace -d "$OUT/pmcsq_c3" -o run --output-format csv -- python bench.py --steps 30 --warmup 3 --no-cpu --no-icp --streams '' --pipeline 0 &&
+    pmcsq) run pmcsq_c3 300 timeout -s KILL 200 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace -d "$OUT/pmcsq_c3" -o run --output-format csv -- python bench.py --full --steps 30 --warmup 3 --no-cpu --no-icp --streams '' --pipeline 0 &&
            run pmcsq_icp 300 timeout -s KILL 200 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace -d "$OUT/pmcsq_icp" -o run --output-format csv -- python scripts/icp_ab.py 1.0 1 &&
            python scripts/pmc_sq_summary.py "$OUT/pmcsq_c3" "$OUT/pmcsq_c3.json" > "$OUT/pmcsq_c3_summary.txt" 2>&1;
            python scripts/pmc_sq_summary.py "$OUT/pmcsq_icp" "$OUT/pmcsq_icp.json" > "$OUT/pmcsq_icp_summary.txt" 2>&1; true ;;
@@ -103,25 +103,25 @@ for c in pc: print(c['k'], round(c['ms'], 3), round(c['submaps_ms'], 3), round(c
            run prep_prof 300 rocprofv3 --kernel-trace --stats -d "$OUT/prep_prof" -o run --output-format csv -- python scripts/prep_timing.py 40 ;;
     setupfid) run icp_setup_fid 300 env LIO_ICP_ORDER=2 python scripts/icp_setup_timing.py &&
            run icp_setup_fid_b 300 env LIO_ICP_ORDER=2 python scripts/icp_setup_timing.py ;;
-    c5prep) run c5_prep_profile 400 bash -c "LIO_PREP_PROFILE=1 python bench.py --config C5 --steps 20 --warmup 2 --no-icp --cpu-scans 2 --cpu-warmup 1 --pipeline 12 --streams '' > $OUT/c5prep.log 2> $OUT/c5prep.err && python scripts/prep_profile_summary.py $OUT/c5prep.err" ;;
+    c5prep) run c5_prep_profile 400 bash -c "LIO_PREP_PROFILE=1 python bench.py --full --config C5 --steps 20 --warmup 2 --no-icp --cpu-scans 2 --cpu-warmup 1 --pipeline 12 --streams '' > $OUT/c5prep.log 2> $OUT/c5prep.err && python scripts/prep_profile_summary.py $OUT/c5prep.err" ;;
     fidprof) run fid_prof 300 env LIO_ICP_ORDER=2 rocprofv3 --kernel-trace --stats -d "$OUT/fidprof" -o run --output-format csv -- python scripts/icp_ab.py 1.0 1 ;;
     maprec) runs pytest_maprec 600 python -u -m pytest tests/test_gpu_map.py tests/test_gpu_pipeline.py -x -v -p no:cacheprovider --timeout 500 --timeout-method thread ;;
     fid)   runs pytest_fid 900 python -u -m pytest tests/test_gpu_seqsum.py tests/test_gpu_icp.py -k "seqsum or fidelity or double" -x -v -s -p no:cacheprovider --timeout 300 --timeout-method thread &&
            run icp_fid_time 300 env LIO_ICP_ORDER=2 python scripts/icp_ab.py 1.0 5 &&
            run icp_fid_time1 300 env LIO_ICP_ORDER=1 python scripts/icp_ab.py 1.0 3 ;;
-    c3)    run bench_c3 600 python bench.py --config C3 --steps 60 --warmup 5 --no-icp --cpu-scans 10 --cpu-warmup 2 --pipeline 12 ;;
-    c2)    run bench_c2 600 python bench.py --config C2 --steps 200 --warmup 20 --no-icp --cpu-scans 20 --cpu-warmup 2 --streams '' ;;
-    c5)    run bench_c5 600 python bench.py --config C5 --steps 200 --warmup 20 --no-icp --cpu-scans 10 --cpu-warmup 2 --pipeline 12 --streams '' ;;
+    c3)    run bench_c3 600 python bench.py --full --config C3 --steps 60 --warmup 5 --no-icp --cpu-scans 10 --cpu-warmup 2 --pipeline 12 ;;
+    c2)    run bench_c2 600 python bench.py --full --config C2 --steps 200 --warmup 20 --no-icp --cpu-scans 20 --cpu-warmup 2 --streams '' ;;
+    c5)    run bench_c5 600 python bench.py --full --config C5 --steps 200 --warmup 20 --no-icp --cpu-scans 10 --cpu-warmup 2 --pipeline 12 --streams '' ;;
     ppprof) run rocprof_pipeline 600 rocprofv3 --kernel-trace --memory-copy-trace --stats -d "$OUT/ppprof" -o run \
-               --output-format csv -- python bench.py --config C3 --steps 5 --warmup 2 --no-icp --no-cpu --pipeline 12 ;;
+               --output-format csv -- python bench.py --full --config C3 --steps 5 --warmup 2 --no-icp --no-cpu --pipeline 12 ;;
     rehearse) LIO_BENCH_REHEARSE=1 run rehearse2 500 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-               --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 100 --warmup 10 --icp-reps 2 ;;
+               --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 2 --steps 100 --warmup 10 --icp-reps 2 ;;
     prof)  run rocprof 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv \
-               -- python bench.py --steps 100 --warmup 10 --no-cpu --icp-reps 3 --streams '' --pipeline 0 ;;
+               -- python bench.py --full --steps 100 --warmup 10 --no-cpu --icp-reps 3 --streams '' --pipeline 0 ;;
     pmc)   run pmc_fetch 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d "$OUT/pmc_fetch" -o run --output-format csv \
-               -- python bench.py --steps 30 --warmup 3 --no-cpu --no-icp --streams '' --pipeline 0 &&
+               -- python bench.py --full --steps 30 --warmup 3 --no-cpu --no-icp --streams '' --pipeline 0 &&
            run pmc_write 600 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d "$OUT/pmc_write" -o run --output-format csv \
-               -- python bench.py --steps 30 --warmup 3 --no-cpu --no-icp --streams '' --pipeline 0 ;;
+               -- python bench.py --full --steps 30 --warmup 3 --no-cpu --no-icp --streams '' --pipeline 0 ;;
     pmcicp) run pmc_icp 900 bash scripts/pmc_icp.sh "$TAG/pmcicp" ;;
     pmcfid) PMC_SCRIPT="scripts/icp_ab.py 1.0 1" PMC_FILTER="seq_|pcl_" run pmc_fid 900 bash scripts/pmc_icp.sh "$TAG/pmcfid" ;;
     fullsize) run pytest_fullsize 900 python -u -m pytest tests/test_gpu_fullsize.py -x -v -s -p no:cacheprovider --timeout 600 --timeout-method thread ;;
@@ -143,7 +143,7 @@ for c in pc: print(c['k'], round(c['ms'], 3), round(c['submaps_ms'], 3), round(c
     icptrace) run icp_trace 300 rocprofv3 --kernel-trace -d "$OUT/icptrace" -o run --output-format csv -- python scripts/icp_ab.py 1.0 1 ;;
     rccl)  run rccl_one_gpu 240 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
                --master-port 29531 scripts/rccl_one_gpu.py ;;
-    watchdog) LIO_BENCH_REHEARSE=1 run watchdog2 300 python bench.py --gpus 2 --steps 20 --warmup 2 --pipeline 0 --no-cpu --streams '' --icp-reps 1 --watchdog-s 0.5 ;;
+    watchdog) LIO_BENCH_REHEARSE=1 run watchdog2 300 python bench.py --full --gpus 2 --steps 20 --warmup 2 --pipeline 0 --no-cpu --streams '' --icp-reps 1 --watchdog-s 0.5 ;;
     icp5)  runs pytest_icp5 900 python -u -m pytest tests/test_gpu_icp.py tests/test_gpu_dist.py tests/test_golden.py tests/test_gpu_parity.py tests/test_gpu_fullsize.py -k "icp or ICP or sharded" -x -v -p no:cacheprovider --timeout 600 --timeout-method thread ;;
     icpt)  run icp_time2 300 python scripts/icp_ab.py 1.0 5 &&
            run icp_time_double 300 env LIO_ICP_ORDER=-1 python scripts/icp_ab.py 1.0 5 ;;

@@ -9,7 +9,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for q in ("4", "8", "16"):
     env = dict(os.environ, GPU_MAX_HW_QUEUES=q)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "50", "--warmup", "5", "--no-cpu",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "50", "--warmup", "5", "--no-cpu",
                         "--no-icp", "--pipeline", "0", "--streams", "1,2,4,8"], capture_output=True, text=True,
                        env=env, timeout=400)
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith('{"metric"')]
