@@ -21,6 +21,7 @@
 #include "lio_error.hpp"
 #include "lio_kernels.hpp"
 #include "lio_filter.hpp"
+#include "lio_denoise.hpp"
 #include "lio_pool.hpp"
 #include "lio_mapupd.hpp"
 
@@ -215,7 +216,8 @@ int lio_abi_struct_sizes(int64_t* out, int n) {
                           (int64_t)sizeof(lio_icp_params),   (int64_t)sizeof(lio_icp_result),
                           (int64_t)sizeof(lio_localmap),     (int64_t)sizeof(lio_incremental_stats),
                           (int64_t)sizeof(lio_imu_pose),     (int64_t)sizeof(lio_scan_prep_params),
-                          (int64_t)sizeof(lio_cloud_field),  (int64_t)sizeof(lio_kernel_timing)};
+                          (int64_t)sizeof(lio_cloud_field),  (int64_t)sizeof(lio_kernel_timing),
+                          (int64_t)sizeof(lio_denoise_params)};
     constexpr int kN = (int)(sizeof(sz) / sizeof(sz[0]));
     if (out)
         for (int i = 0; i < n && i < kN; ++i) out[i] = sz[i];
@@ -1071,6 +1073,7 @@ struct lio_filter {
     int64_t T_cap = 0;
     lio::ImuPose* d_poses = nullptr;
     int64_t poses_cap = 0;
+    lio::DenoiseBuf dn;  // lio_sor_filter / lio_radius_first_seed / lio_denoise_slam_map
 };
 
 static int filter_status(int rc, const char* what) {
@@ -1281,6 +1284,7 @@ int lio_filter_destroy(lio_filter* f) {
     (void)hipSetDevice(f->dev);
     (void)hipStreamSynchronize(f->st);
     lio::filter_free(f->b);
+    lio::denoise_free(f->dn);
     for (void* q : {(void*)f->d_in, (void*)f->d_out, (void*)f->d_seg, (void*)f->d_T, (void*)f->d_poses})
         if (q) (void)hipFree(q);
     (void)hipStreamDestroy(f->st);
@@ -1304,6 +1308,102 @@ int lio_voxel_grid(lio_filter* f, const float* pts, int64_t n, int stride, const
     rc = lio::voxel_grid(f->b, f->d_in, n, stride, leaf, f->d_out, &m, f->st);
     if (rc) return filter_status(rc, "lio_voxel_grid");
     if (m) HIP_TRY(hipMemcpyAsync(out, f->d_out, (size_t)m * stride * sizeof(float), hipMemcpyDeviceToHost, f->st));
+    HIP_TRY(hipStreamSynchronize(f->st));
+    *n_out = m;
+    return LIO_OK;
+}
+
+// ---- statistical outlier removal, first-seed radius query, intensity map denoise (lio_denoise.hip) ----
+// a NULL handle without a device is the missing device (lio_filter_create cannot have succeeded), not a bad argument
+static int denoise_handle(lio_filter* f, const char* what) {
+    if (f) return LIO_OK;
+    const int rc = check_device(0);
+    if (rc) return rc;
+    return fail(LIO_ERR_ARG, std::string(what) + ": handle is NULL");
+}
+
+// status of a lio_denoise.hip driver: every -2 it returns has just left the failed HIP call's text in
+// last_error() (its DCHK), taken here before fail() replaces it
+static int denoise_status(int rc, const char* what) {
+    if (rc != -2) return filter_status(rc, what);
+    const std::string detail = lio::last_error();
+    return fail(LIO_ERR_HIP, std::string(what) + " failed (" + detail + ")");
+}
+
+int lio_sor_filter(lio_filter* f, const float* pts, int64_t n, int stride, int mean_k, double stddev_mul, int negative,
+                   float* out, int64_t* n_out, float* distances_opt, double* stats4_opt) {
+    int rc = denoise_handle(f, "lio_sor_filter");
+    if (rc) return rc;
+    if (!n_out || n < 0 || (n > 0 && (!pts || !out)) || stride < 3 || stride > lio::kMaxFields || mean_k < 1 ||
+        mean_k > 255 || n >= (int64_t)1 << 30)
+        return fail(LIO_ERR_ARG, "lio_sor_filter: bad arguments");
+    *n_out = 0;
+    HIP_TRY(hipSetDevice(f->dev));
+    if (n > 0) {
+        rc = grow(&f->d_in, f->in_cap, n * stride);
+        if (!rc) rc = grow(&f->d_out, f->out_cap, n * stride);
+        if (rc) return rc;
+        HIP_TRY(hipMemcpyAsync(f->d_in, pts, (size_t)n * stride * sizeof(float), hipMemcpyHostToDevice, f->st));
+    }
+    int64_t m = 0;
+    rc = lio::sor_filter(f->dn, f->d_in, n, stride, mean_k, stddev_mul, negative != 0, f->d_out, &m, distances_opt,
+                         stats4_opt, f->st);
+    if (rc) return denoise_status(rc, "lio_sor_filter");
+    if (m) HIP_TRY(hipMemcpyAsync(out, f->d_out, (size_t)m * stride * sizeof(float), hipMemcpyDeviceToHost, f->st));
+    HIP_TRY(hipStreamSynchronize(f->st));
+    *n_out = m;
+    return LIO_OK;
+}
+
+int lio_radius_first_seed(lio_filter* f, const float* pts, int64_t n, int stride, const float* seeds_xyz, int64_t ns,
+                          float radius, int32_t* seed_out, float* d2_out_opt) {
+    int rc = denoise_handle(f, "lio_radius_first_seed");
+    if (rc) return rc;
+    if (n < 0 || ns < 0 || (n > 0 && (!pts || !seed_out)) || (ns > 0 && !seeds_xyz) || stride < 3 ||
+        stride > lio::kMaxFields || !(radius >= 0.f) || !std::isfinite(radius) || n >= (int64_t)1 << 30 ||
+        ns >= (int64_t)1 << 30)
+        return fail(LIO_ERR_ARG, "lio_radius_first_seed: bad arguments");
+    if (n == 0) return LIO_OK;
+    HIP_TRY(hipSetDevice(f->dev));
+    rc = grow(&f->d_in, f->in_cap, n * stride);
+    if (rc) return rc;
+    rc = lio::denoise_reserve(f->dn, std::max(n, ns));
+    if (rc) return denoise_status(rc, "lio_radius_first_seed");
+    HIP_TRY(hipMemcpyAsync(f->d_in, pts, (size_t)n * stride * sizeof(float), hipMemcpyHostToDevice, f->st));
+    if (ns) HIP_TRY(hipMemcpyAsync(f->dn.seeds_xyz, seeds_xyz, (size_t)ns * 3 * sizeof(float), hipMemcpyHostToDevice, f->st));
+    rc = lio::radius_first_seed(f->dn, f->d_in, n, stride, f->dn.seeds_xyz, ns, radius, f->dn.seed_id, f->dn.seed_d2,
+                                f->st);
+    if (rc) return denoise_status(rc, "lio_radius_first_seed");
+    HIP_TRY(hipMemcpyAsync(seed_out, f->dn.seed_id, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, f->st));
+    if (d2_out_opt)
+        HIP_TRY(hipMemcpyAsync(d2_out_opt, f->dn.seed_d2, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, f->st));
+    HIP_TRY(hipStreamSynchronize(f->st));
+    return LIO_OK;
+}
+
+int lio_denoise_slam_map(lio_filter* f, const float* pts, int64_t n, const lio_denoise_params* p, float* out,
+                         int64_t* n_out, int64_t* counts5_opt) {
+    int rc = denoise_handle(f, "lio_denoise_slam_map");
+    if (rc) return rc;
+    if (!p || !n_out || n < 0 || (n > 0 && (!pts || !out)) || p->mean_k < 1 || p->mean_k > 255 ||
+        !(p->cluster_seed_radius >= 0.f) || !(p->denoise_radius >= 0.f) || !std::isfinite(p->cluster_seed_radius) ||
+        !std::isfinite(p->denoise_radius) || n >= (int64_t)1 << 29)
+        return fail(LIO_ERR_ARG, "lio_denoise_slam_map: bad arguments");
+    *n_out = 0;
+    if (counts5_opt)
+        for (int k = 0; k < 5; ++k) counts5_opt[k] = 0;
+    if (n == 0) return LIO_OK;
+    HIP_TRY(hipSetDevice(f->dev));
+    rc = grow(&f->d_in, f->in_cap, n * 4);
+    if (!rc) rc = grow(&f->d_out, f->out_cap, n * 4);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(f->d_in, pts, (size_t)n * 4 * sizeof(float), hipMemcpyHostToDevice, f->st));
+    const lio::DenoiseParams dp{p->seed_thres,  p->cluster_seed_radius, p->denoise_radius,
+                                p->noise_thres, p->mean_k,              p->stddev_mul};
+    int64_t m = 0;
+    rc = lio::denoise_slam_map(f->dn, f->d_in, n, dp, f->d_out, &m, counts5_opt, f->st);
+    if (rc) return denoise_status(rc, "lio_denoise_slam_map");
+    if (m) HIP_TRY(hipMemcpyAsync(out, f->d_out, (size_t)m * 4 * sizeof(float), hipMemcpyDeviceToHost, f->st));
     HIP_TRY(hipStreamSynchronize(f->st));
     *n_out = m;
     return LIO_OK;

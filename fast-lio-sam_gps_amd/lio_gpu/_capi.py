@@ -45,6 +45,7 @@ EXPORTS = [
     "lio_map_set_test_limits", "lio_rccl_unique_id", "lio_icp_set_shard_rccl", "lio_icp_set_shard_shm",
     "lio_shm_exchange_open", "lio_shm_exchange_allgather", "lio_shm_exchange_close", "lio_shm_exchange_set_timeout",
     "lio_seq_shard_offsets", "lio_seq_shard_merge",
+    "lio_sor_filter", "lio_radius_first_seed", "lio_denoise_slam_map",
 ]
 
 
@@ -128,6 +129,11 @@ class KernelTiming(C.Structure):
                 ("icp_nn_launches", C.c_int64), ("icp_nn_ms", C.c_double)]
 
 
+class DenoiseParams(C.Structure):
+    _fields_ = [("seed_thres", C.c_float), ("cluster_seed_radius", C.c_float), ("denoise_radius", C.c_float),
+                ("noise_thres", C.c_float), ("mean_k", C.c_int), ("stddev_mul", C.c_float)]
+
+
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.POINTER(C.c_double), C.c_int64, C.POINTER(C.c_double), C.c_void_p)
 # lio_allgather_dev_fn(d_send, n, d_recv, stream, user): device pointers, enqueue on `stream`
 ALLGATHER_DEV_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p)
@@ -197,6 +203,12 @@ def _declare(L):
                                      C.POINTER(Pose), fp, C.POINTER(C.c_int64)]),
         "lio_scan_preprocess": (C.c_int, [vp, fp, C.c_int64, C.c_int, C.POINTER(ScanPrepParams), C.POINTER(ImuPose),
                                           C.c_int, C.POINTER(Pose), C.POINTER(C.c_int64)]),
+        "lio_sor_filter": (C.c_int, [vp, fp, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_int, fp,
+                                     C.POINTER(C.c_int64), fp, dp]),
+        "lio_radius_first_seed": (C.c_int, [vp, fp, C.c_int64, C.c_int, fp, C.c_int64, C.c_float,
+                                            C.POINTER(C.c_int32), fp]),
+        "lio_denoise_slam_map": (C.c_int, [vp, fp, C.c_int64, C.POINTER(DenoiseParams), fp, C.POINTER(C.c_int64),
+                                           C.POINTER(C.c_int64)]),
         "lio_ctx_create": (C.c_int, [vp, C.POINTER(MatchParams), C.POINTER(vp)]),
         "lio_ctx_destroy": (C.c_int, [vp]),
         "lio_scan_set": (C.c_int, [vp, fp, C.c_int64]),
@@ -293,7 +305,7 @@ def lib():
 
 # the ctypes mirrors of lio_abi_struct_sizes' structs, in its order
 _ABI_STRUCTS = ("MapParams", "MatchParams", "Pose", "State", "IeskfParams", "IeskfStats", "IcpParams", "IcpResult",
-                "LocalMap", "IncrementalStats", "ImuPose", "ScanPrepParams", "CloudField", "KernelTiming")
+                "LocalMap", "IncrementalStats", "ImuPose", "ScanPrepParams", "CloudField", "KernelTiming", "DenoiseParams")
 
 
 def _check_abi(L):

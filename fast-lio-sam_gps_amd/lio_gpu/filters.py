@@ -8,6 +8,8 @@
   keyframe, concatenation, ``voxelizePcd``
 * :class:`ScanPreprocessor` — FAST-LIO ``Preprocess`` selection +
   ``ImuProcess::UndistortPcl`` + ``downSizeFilterSurf`` for one raw scan
+* :class:`StatisticalOutlierRemoval`, :func:`radius_first_seed`, :func:`denoise_slam_map` — the back
+  end's intensity denoise (fast_lio_sam.cpp:941-1008, 575-646, 332-365) and its parts
 
 Point records are float rows ``[x, y, z, attr...]`` (3..8 floats); PCL's
 PointXYZI is ``stride = 4``, FAST-LIO's PointXYZINormal-with-time is
@@ -62,6 +64,79 @@ class VoxelGrid(_Handle):
         m = C.c_int64(0)
         check(lib().lio_voxel_grid(self._h, _fp(pts2), len(pts2), stride, _fp(self.leaf), _fp(out), C.byref(m)))
         return out[: m.value].copy()
+
+
+def _rows(pts):
+    """float32 records as a contiguous (n, stride) array (an empty cloud keeps its stride)"""
+    pts = np.ascontiguousarray(pts, dtype=np.float32)
+    if pts.size == 0:
+        return pts.reshape(0, pts.shape[-1] if pts.ndim > 1 and pts.shape[-1] else 3)
+    return pts.reshape(len(pts), -1)
+
+
+class StatisticalOutlierRemoval(_Handle):
+    """``pcl::StatisticalOutlierRemoval``: the mean distance to the ``mean_k`` nearest neighbours per point,
+    points farther than ``mean + stddev_mul * stddev`` removed (``negative``: the others), order kept.
+    After :meth:`filter`: ``distances`` (per input point, 0 where not counted) and ``stats`` = mean, stddev,
+    threshold, counted points."""
+
+    def __init__(self, mean_k: int = 50, stddev_mul: float = 1.0, negative: bool = False, device: int = 0):
+        super().__init__(device)
+        self.setMeanK(mean_k)
+        self.setStddevMulThresh(stddev_mul)
+        self.setNegative(negative)
+        self.distances = np.zeros(0, np.float32)
+        self.stats = np.full(4, np.nan)
+
+    def setMeanK(self, k):
+        self.mean_k = int(k)
+
+    def setStddevMulThresh(self, m):
+        self.stddev_mul = float(m)
+
+    def setNegative(self, negative):
+        self.negative = bool(negative)
+
+    def filter(self, pts: np.ndarray) -> np.ndarray:
+        pts2 = _rows(pts)
+        out = np.empty_like(pts2)
+        self.distances = np.zeros(len(pts2), np.float32)
+        self.stats = np.zeros(4, np.float64)
+        m = C.c_int64(0)
+        check(lib().lio_sor_filter(self._h, _fp(pts2), len(pts2), pts2.shape[1], self.mean_k, self.stddev_mul,
+                                   int(self.negative), _fp(out), C.byref(m), _fp(self.distances),
+                                   self.stats.ctypes.data_as(C.POINTER(C.c_double))))
+        return out[: m.value].copy()
+
+
+def radius_first_seed(pts, seeds_xyz, radius: float, handle: _Handle | None = None):
+    """Per cloud point the lowest seed index within ``radius`` (strict, float squared distances; -1: none)
+    and that squared distance: ``KdTreeFLANN::radiusSearch`` per seed, turned round."""
+    h = handle or _Handle()
+    pts2 = _rows(pts)
+    seeds = np.ascontiguousarray(np.asarray(seeds_xyz, np.float32).reshape(-1, 3))
+    seed = np.full(len(pts2), -1, np.int32)
+    d2 = np.zeros(len(pts2), np.float32)
+    check(lib().lio_radius_first_seed(h._h, _fp(pts2), len(pts2), pts2.shape[1], _fp(seeds),
+                                      len(seeds), float(radius), seed.ctypes.data_as(C.POINTER(C.c_int32)), _fp(d2)))
+    return seed, d2
+
+
+def denoise_slam_map(pts, seed_thres=2800.0, cluster_seed_radius=1.0, denoise_radius=0.5, noise_thres=2700.0,
+                     mean_k=50, stddev_mul=1.0, handle: _Handle | None = None):
+    """``FastLioSam::denoise_slam_map`` (fast_lio_sam.cpp:941-1008) on ``[x, y, z, intensity]`` rows; the
+    defaults are the reference's (fast_lio_sam.cpp:89-96; its config.yaml sets 0.1, 200 and 0.2).
+    Returns the denoised map (denoised segment, then the remained points) and ``counts`` = seeds, segmented,
+    after SOR, denoised, remained."""
+    h = handle or _Handle()
+    pts = np.ascontiguousarray(pts, dtype=np.float32).reshape(-1, 4)
+    out = np.empty_like(pts)
+    counts = np.zeros(5, np.int64)
+    m = C.c_int64(0)
+    p = _capi.DenoiseParams(seed_thres, cluster_seed_radius, denoise_radius, noise_thres, int(mean_k), stddev_mul)
+    check(lib().lio_denoise_slam_map(h._h, _fp(pts), len(pts), C.byref(p), _fp(out), C.byref(m),
+                                     counts.ctypes.data_as(C.POINTER(C.c_int64))))
+    return out[: m.value].copy(), counts
 
 
 def voxelize_submap(clouds, poses, voxel_res: float, handle: VoxelGrid | None = None) -> np.ndarray:

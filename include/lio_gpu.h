@@ -61,7 +61,7 @@ const char* lio_build_info(void);
 int64_t lio_alloc_count(void);
 /* ABI guard (no device needed): sizeof of the public structs, in the order map_params, match_params, pose,
  * state, ieskf_params, ieskf_stats, icp_params, icp_result, localmap, incremental_stats, imu_pose,
- * scan_prep_params, cloud_field, kernel_timing — the first min(n, count) into out; returns the count.
+ * scan_prep_params, cloud_field, kernel_timing, denoise_params — the first min(n, count) into out; returns the count.
  * A binding built against another header version must refuse the library (an output struct of the wrong
  * size is a buffer overrun: round 4's A/B of a round-2 build segfaulted at exit that way).           */
 int lio_abi_struct_sizes(int64_t* out, int n);
@@ -465,6 +465,53 @@ int lio_scan_get_undistorted(lio_ctx* c, float* out, int64_t cap_points, int64_t
  * out = NULL: count only.                                                                          */
 int lio_scan_keyframe_cloud(lio_ctx* c, const lio_pose* pose, const double* T16, float* out, int64_t cap_points,
                             int64_t* n_points);
+
+/* ---------------------------------- outlier removal and the intensity map denoise
+ * The back end's denoise (fast_lio_sam.cpp:262-365, 575-680, 941-1008; config.yaml:32-42) and its parts.
+ * Squared distances are float ((dx*dx + dy*dy) + dz*dz) everywhere; non-finite points are nobody's neighbour. */
+
+/* pcl::StatisticalOutlierRemoval<PointT>::applyFilter, PCL 1.10 [U]: pts is n x stride floats (x, y, z first;
+ * stride 3..8), mean_k 1..255.  Per finite point the mean distance to its mean_k nearest neighbours (the
+ * mean_k + 1 smallest squared distances, itself included, the first dropped; double square roots added in
+ * ascending order); non-finite points, and every point when fewer than mean_k + 1 finite points exist, get
+ * distance 0 and are not counted.  mean / stddev over the counted points in PCL's double loop, threshold =
+ * mean + stddev_mul * stddev; a point is removed when its distance is > threshold (negative: when <=), so a
+ * NaN threshold (no counted point) keeps every point.  out: the kept records in input order (capacity
+ * n x stride).  distances_opt (n, may be NULL); stats4_opt (may be NULL) = mean, stddev, threshold, counted. */
+int lio_sor_filter(lio_filter* f, const float* pts, int64_t n, int stride, int mean_k, double stddev_mul, int negative,
+                   float* out, int64_t* n_out, float* distances_opt, double* stats4_opt);
+
+/* KdTreeFLANN::radiusSearch per seed [U], turned round: per cloud point (n x stride records) the lowest index s
+ * of the ns seeds (ns x 3 floats) with squared distance < r2, r2 = (float)((double)radius * radius), strict
+ * (-1: none), and that squared distance (d2_out_opt, may be NULL; 0 where none).  Non-finite points and
+ * seeds never match.                                                                                       */
+int lio_radius_first_seed(lio_filter* f, const float* pts, int64_t n, int stride, const float* seeds_xyz, int64_t ns,
+                          float radius, int32_t* seed_out, float* d2_out_opt);
+
+typedef struct lio_denoise_params { /* /denoise/... (fast_lio_sam.cpp:89-96, config.yaml:32-42) */
+    float seed_thres;          /* 2800 */
+    float cluster_seed_radius; /* 0.1 (config.yaml), 1.0 (source default) */
+    float denoise_radius;      /* 0.5 */
+    float noise_thres;         /* 2700 */
+    int mean_k;                /* sor/MeanK: 200 (config.yaml), 50 (source default) */
+    float stddev_mul;          /* sor/StddevMulThresh: 0.2 (config.yaml), 1.0 (source default) */
+} lio_denoise_params;
+
+/* FastLioSam::denoise_slam_map (fast_lio_sam.cpp:941-1008 with denoise_map :575-646 and
+ * clustering_and_denoise :332-365) on PointXYZI records (n x 4: x, y, z, intensity):
+ *   seeds     = points with intensity > seed_thres, in input order;
+ *   segmented = points with intensity != 0 that have a seed within cluster_seed_radius, ordered by the
+ *               claiming (lowest) seed index, then ascending squared distance to that seed, THEN POINT INDEX
+ *               (the reference leaves equal distances to FLANN's order; the index tie-break is this
+ *               library's contract);
+ *   remained  = points with intensity != 0 that are not segmented, in input order (points whose input
+ *               intensity is exactly 0 disappear, as in the reference);
+ *   denoised  = SOR(mean_k, stddev_mul) of segmented, order kept, then without every point of intensity
+ *               < noise_thres that has a seed within denoise_radius;
+ *   out       = denoised followed by remained (capacity n x 4).
+ * counts5_opt (may be NULL) = seeds, segmented, after SOR, denoised, remained.                             */
+int lio_denoise_slam_map(lio_filter* f, const float* pts, int64_t n, const lio_denoise_params* p, float* out,
+                         int64_t* n_out, int64_t* counts5_opt);
 
 /* ------------------------------------------- wire / disk formats (§8(f) row 4) */
 /* One output column of a packed point record: byte offset, sensor_msgs/PointField datatype

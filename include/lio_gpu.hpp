@@ -13,6 +13,8 @@
 //   * VoxelGrid<PointT>, submap_voxelize, preprocess_scan, savePCDFileBinary,
 //     loadPCDFile ~ pcl::VoxelGrid, setSrcAndDstCloud's transformPcd +
 //     voxelizePcd, Preprocess + UndistortPcl, pcl::io PCD I/O
+//   * StatisticalOutlierRemoval<PointT>, DenoiseConfig, denoise_slam_map ~ pcl::StatisticalOutlierRemoval and
+//     FastLioSam::denoise_slam_map (fast_lio_sam.cpp:941-1008)
 // PointType is any struct with float members x, y, z (pcl::PointXYZI,
 // pcl::PointXYZINormal, ...).  Errors throw lio_gpu::Error carrying
 // lio_last_error(); there is no CPU fallback behind any call.
@@ -564,6 +566,65 @@ private:
 struct PointXYZI {  // pcl::PointXYZI's float fields (x, y, z, intensity)
     float x, y, z, intensity;
 };
+
+// pcl::StatisticalOutlierRemoval<PointT>: setInputCloud / setMeanK / setStddevMulThresh / setNegative / filter
+// (clustering_and_denoise, fast_lio_sam.cpp:332-365).  Kept points in input order.
+template <typename PointT>
+class StatisticalOutlierRemoval {
+public:
+    explicit StatisticalOutlierRemoval(FilterGPU& f) : f_(f) {}
+    void setInputCloud(const std::vector<PointT>* cloud) { in_ = cloud; }
+    void setMeanK(int k) { mean_k_ = k; }
+    void setStddevMulThresh(double m) { std_mul_ = m; }
+    void setNegative(bool negative) { negative_ = negative; }
+    void filter(std::vector<PointT>& out) {
+        if (!in_) throw Error(LIO_ERR_ARG, "StatisticalOutlierRemoval: no input cloud");
+        std::vector<PointT> kept(in_->size());  // `out` may be the input cloud
+        int64_t n = 0;
+        check(lio_sor_filter(f_.handle(), reinterpret_cast<const float*>(in_->data()), (int64_t)in_->size(),
+                             float_stride<PointT>(), mean_k_, std_mul_, negative_ ? 1 : 0,
+                             reinterpret_cast<float*>(kept.data()), &n, nullptr, stats_),
+              "StatisticalOutlierRemoval::filter");
+        kept.resize((size_t)n);
+        out.swap(kept);
+    }
+    // mean, stddev, threshold, counted points of the last filter()
+    const double* stats() const { return stats_; }
+
+private:
+    FilterGPU& f_;
+    const std::vector<PointT>* in_ = nullptr;
+    int mean_k_ = 1;        // PCL's defaults
+    double std_mul_ = 0.0;
+    bool negative_ = false;
+    double stats_[4] = {0, 0, 0, 0};
+};
+
+struct DenoiseConfig {  // fast_lio_sam.h:123-129, defaults of fast_lio_sam.cpp:89-96 (config.yaml:32-42 sets 0.1, 200, 0.2)
+    bool denoise_en = false;
+    float seed_thres = 2800.0;
+    float denoise_radius = 0.5;
+    float cluster_seed_radius = 1.0;
+    float noise_thres = 2700.0;
+    int MeanK = 50;
+    float StddevMulThresh = 1.0;
+};
+
+// FastLioSam::denoise_slam_map(slam_map) (fast_lio_sam.cpp:941-1008): replaces the cloud in place.  Points at
+// equal distance from their seed follow in index order (lio_gpu.h).  counts5 (optional): seeds, segmented, after
+// SOR, denoised, remained.
+inline void denoise_slam_map(FilterGPU& f, const DenoiseConfig& c, std::vector<PointXYZI>& slam_map,
+                             int64_t* counts5 = nullptr) {
+    const lio_denoise_params p{c.seed_thres, c.cluster_seed_radius, c.denoise_radius, c.noise_thres, c.MeanK,
+                               c.StddevMulThresh};
+    std::vector<PointXYZI> out(slam_map.size());
+    int64_t n = 0;
+    check(lio_denoise_slam_map(f.handle(), reinterpret_cast<const float*>(slam_map.data()), (int64_t)slam_map.size(), &p,
+                               reinterpret_cast<float*>(out.data()), &n, counts5),
+          "denoise_slam_map");
+    out.resize((size_t)n);
+    slam_map.swap(out);
+}
 
 struct PosePcd {  // pose_pcd.hpp:7-19
     std::vector<PointXYZI> pcd_;
