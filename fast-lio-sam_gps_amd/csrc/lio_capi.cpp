@@ -22,6 +22,7 @@
 #include "lio_kernels.hpp"
 #include "lio_filter.hpp"
 #include "lio_denoise.hpp"
+#include "lio_cluster.hpp"
 #include "lio_pool.hpp"
 #include "lio_mapupd.hpp"
 
@@ -1074,6 +1075,7 @@ struct lio_filter {
     lio::ImuPose* d_poses = nullptr;
     int64_t poses_cap = 0;
     lio::DenoiseBuf dn;  // lio_sor_filter / lio_radius_first_seed / lio_denoise_slam_map
+    lio::ClusterBuf cl;  // lio_euclidean_clusters (with dn: the grid, the sorts and the scan)
 };
 
 static int filter_status(int rc, const char* what) {
@@ -1285,6 +1287,7 @@ int lio_filter_destroy(lio_filter* f) {
     (void)hipStreamSynchronize(f->st);
     lio::filter_free(f->b);
     lio::denoise_free(f->dn);
+    lio::cluster_free(f->cl);
     for (void* q : {(void*)f->d_in, (void*)f->d_out, (void*)f->d_seg, (void*)f->d_T, (void*)f->d_poses})
         if (q) (void)hipFree(q);
     (void)hipStreamDestroy(f->st);
@@ -1406,6 +1409,44 @@ int lio_denoise_slam_map(lio_filter* f, const float* pts, int64_t n, const lio_d
     if (m) HIP_TRY(hipMemcpyAsync(out, f->d_out, (size_t)m * 4 * sizeof(float), hipMemcpyDeviceToHost, f->st));
     HIP_TRY(hipStreamSynchronize(f->st));
     *n_out = m;
+    return LIO_OK;
+}
+
+// ---- Euclidean cluster extraction with per-cluster bounding boxes (lio_cluster.hip) ----
+int lio_euclidean_clusters(lio_filter* f, const float* pts, int64_t n, int stride, float tolerance, int64_t min_size,
+                           int64_t max_size, int32_t* labels_out, int64_t* n_clusters, int64_t cap_clusters,
+                           int64_t* offsets_opt, int32_t* indices_opt, float* aabb6_opt, int64_t* stats4_opt) {
+    int rc = denoise_handle(f, "lio_euclidean_clusters");
+    if (rc) return rc;
+    if (!n_clusters || n < 0 || n >= (int64_t)1 << 31 || (n > 0 && (!pts || !labels_out)) || stride < 3 ||
+        stride > lio::kMaxFields || !(tolerance > 0.f) || !std::isfinite(tolerance) || min_size < 1 || cap_clusters < 0)
+        return fail(LIO_ERR_ARG, "lio_euclidean_clusters: bad arguments");
+    *n_clusters = 0;
+    if (stats4_opt)
+        for (int k = 0; k < 4; ++k) stats4_opt[k] = 0;
+    if (offsets_opt) offsets_opt[0] = 0;
+    if (n == 0) return LIO_OK;
+    HIP_TRY(hipSetDevice(f->dev));
+    rc = grow(&f->d_in, f->in_cap, n * stride);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(f->d_in, pts, (size_t)n * stride * sizeof(float), hipMemcpyHostToDevice, f->st));
+    lio::ClusterCounts cc;
+    rc = lio::euclidean_clusters(f->dn, f->cl, f->d_in, n, stride, tolerance, min_size, max_size, cap_clusters, &cc, f->st);
+    if (rc) return denoise_status(rc, "lio_euclidean_clusters");
+    const int64_t m = std::min(cc.clusters, cap_clusters);
+    HIP_TRY(hipMemcpyAsync(labels_out, f->cl.labels, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, f->st));
+    if (indices_opt && cc.clustered_points)
+        HIP_TRY(hipMemcpyAsync(indices_opt, f->cl.indices, (size_t)cc.clustered_points * sizeof(int32_t),
+                               hipMemcpyDeviceToHost, f->st));
+    if (offsets_opt)
+        HIP_TRY(hipMemcpyAsync(offsets_opt, f->cl.offsets, (size_t)(m + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, f->st));
+    if (aabb6_opt && m)
+        HIP_TRY(hipMemcpyAsync(aabb6_opt, f->cl.aabb, (size_t)m * 6 * sizeof(float), hipMemcpyDeviceToHost, f->st));
+    HIP_TRY(hipStreamSynchronize(f->st));
+    *n_clusters = cc.clusters;
+    if (stats4_opt)
+        stats4_opt[0] = cc.finite, stats4_opt[1] = cc.components, stats4_opt[2] = cc.clusters,
+        stats4_opt[3] = cc.clustered_points;
     return LIO_OK;
 }
 

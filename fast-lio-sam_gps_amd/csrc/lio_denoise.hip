@@ -463,7 +463,9 @@ __global__ void gather_rows4_kernel(const float* __restrict__ in, const uint32_t
     reinterpret_cast<float4*>(out)[t] = reinterpret_cast<const float4*>(in)[idx[t]];
 }
 
-// ---- host side ------------------------------------------------------------------------------------------
+}  // namespace
+
+// ---- host side (dn_*: shared with lio_cluster.hip through lio_denoise.hpp) ------------------------------
 int dn_sort32(DenoiseBuf& b, int64_t n, int bits, hipStream_t st) {
     size_t bytes = 0;
     DCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, b.keys, b.keys_alt, b.vals, b.vals_alt, (int)n, 0, bits, st));
@@ -504,7 +506,7 @@ int dn_scan_count(DenoiseBuf& b, int64_t n, int64_t* count, hipStream_t st) {
     return 0;
 }
 
-inline int bit_width(uint32_t v) {
+int dn_bit_width(uint32_t v) {
     int b = 0;
     while (v) ++b, v >>= 1;
     return std::max(b, 1);
@@ -518,15 +520,13 @@ int dn_build_grid(DenoiseBuf& b, const float* d_pts, int64_t n, int stride, floa
     dn_minmax_kernel<<<nbp, 256, 0, st>>>(d_pts, n, stride, b.part);
     dn_geom_kernel<<<1, 256, 0, st>>>(b.part, nbp, n, target, fixed_cell, cells_cap, b.geom);
     dn_key_kernel<<<nblk(n), 256, 0, st>>>(d_pts, n, stride, b.geom, cells_cap, b.keys, b.vals);
-    const int rc = dn_sort32(b, n, bit_width(cells_cap), st);
+    const int rc = dn_sort32(b, n, dn_bit_width(cells_cap), st);
     if (rc) return rc;
     dn_start_kernel<<<nblk((int64_t)cells_cap + 1), 256, 0, st>>>(b.keys_alt, n, cells_cap, b.start);
     dn_gather_kernel<<<nblk(n), 256, 0, st>>>(d_pts, n, stride, b.vals_alt, b.g4);
     DCHK(hipGetLastError());
     return 0;
 }
-
-}  // namespace
 
 void denoise_free(DenoiseBuf& b) {
     if (b.arena) (void)hipFree(b.arena);
@@ -680,7 +680,7 @@ int denoise_slam_map(DenoiseBuf& b, const float* d_pts, int64_t n, const Denoise
     if ((rc = dn_scan_count(b, n, &cnt[1], st))) return rc;
     if (cnt[1] > 0) {
         seg_scatter_kernel<<<nblk(n), 256, 0, st>>>(n, b.flags, b.pos, b.seed_id, b.seed_d2, b.idx, b.k64);
-        if ((rc = dn_sort64(b, cnt[1], 32 + bit_width((uint32_t)cnt[0]), st))) return rc;
+        if ((rc = dn_sort64(b, cnt[1], 32 + dn_bit_width((uint32_t)cnt[0]), st))) return rc;
         gather_rows4_kernel<<<nblk(cnt[1]), 256, 0, st>>>(d_pts, b.idx_alt, cnt[1], b.cloud_a);
         // 4. denoise_map: SOR on segmented, then drop intensity < noise_thres with a seed within denoise_radius
         if ((rc = sor_filter(b, b.cloud_a, cnt[1], 4, p.mean_k, (double)p.stddev_mul, false, b.cloud_b, &cnt[2], nullptr,

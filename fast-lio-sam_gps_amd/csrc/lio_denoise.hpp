@@ -56,6 +56,22 @@ void denoise_free(DenoiseBuf& b);
 // every buffer sized for n points (n >= the cloud and the seed count of the calls that follow)
 int denoise_reserve(DenoiseBuf& b, int64_t n);
 
+// The building blocks the searches share (lio_cluster.hip uses them too), after denoise_reserve(b, >= n).  Status
+// as the entry points': 0, or -2 with the failed HIP call's text in last_error().
+// The grid of the finite points of d_pts in b.g4 (x, y, z, input index; cell order) / b.start (CSR offsets;
+// b.start[ncells] = finite points) / b.geom, enqueued (no host wait).  target > 0: cell edge from the density
+// (a 3x3x3 block holds about `target` points); target == 0: the edge is fixed_cell.  Either edge grows until
+// the grid has at most n + 64 cells.  Uses b.keys / b.vals (and their _alt) and b.part.
+int dn_build_grid(DenoiseBuf& b, const float* d_pts, int64_t n, int stride, float target, float fixed_cell,
+                  hipStream_t st);
+// stable radix sorts over the low `bits` bits, enqueued: (b.keys, b.vals) -> (b.keys_alt, b.vals_alt);
+// (b.k64, b.idx) -> (b.k64_alt, b.idx_alt)
+int dn_sort32(DenoiseBuf& b, int64_t n, int bits, hipStream_t st);
+int dn_sort64(DenoiseBuf& b, int64_t n, int bits, hipStream_t st);
+// b.pos = exclusive scan of b.flags[0 .. n]; *count = b.pos[n].  Waits for the stream.
+int dn_scan_count(DenoiseBuf& b, int64_t n, int64_t* count, hipStream_t st);
+int dn_bit_width(uint32_t v);  // bits needed for v, at least 1
+
 // Kernel A, enqueued: d_dist[i] = mean distance of point i to its mean_k nearest neighbours, -1 for a point that
 // is not counted (non-finite, or fewer than mean_k + 1 finite points in the cloud).  A d_dist inside b (b.dist)
 // is read after denoise_reserve(b, n): the arena's pointers are set there.

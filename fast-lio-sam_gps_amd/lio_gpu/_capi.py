@@ -45,7 +45,7 @@ EXPORTS = [
     "lio_map_set_test_limits", "lio_rccl_unique_id", "lio_icp_set_shard_rccl", "lio_icp_set_shard_shm",
     "lio_shm_exchange_open", "lio_shm_exchange_allgather", "lio_shm_exchange_close", "lio_shm_exchange_set_timeout",
     "lio_seq_shard_offsets", "lio_seq_shard_merge",
-    "lio_sor_filter", "lio_radius_first_seed", "lio_denoise_slam_map",
+    "lio_sor_filter", "lio_radius_first_seed", "lio_denoise_slam_map", "lio_euclidean_clusters",
 ]
 
 
@@ -209,6 +209,9 @@ def _declare(L):
                                             C.POINTER(C.c_int32), fp]),
         "lio_denoise_slam_map": (C.c_int, [vp, fp, C.c_int64, C.POINTER(DenoiseParams), fp, C.POINTER(C.c_int64),
                                            C.POINTER(C.c_int64)]),
+        "lio_euclidean_clusters": (C.c_int, [vp, fp, C.c_int64, C.c_int, C.c_float, C.c_int64, C.c_int64,
+                                             C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.c_int64,
+                                             C.POINTER(C.c_int64), C.POINTER(C.c_int32), fp, C.POINTER(C.c_int64)]),
         "lio_ctx_create": (C.c_int, [vp, C.POINTER(MatchParams), C.POINTER(vp)]),
         "lio_ctx_destroy": (C.c_int, [vp]),
         "lio_scan_set": (C.c_int, [vp, fp, C.c_int64]),

@@ -10,6 +10,8 @@
   ``ImuProcess::UndistortPcl`` + ``downSizeFilterSurf`` for one raw scan
 * :class:`StatisticalOutlierRemoval`, :func:`radius_first_seed`, :func:`denoise_slam_map` — the back
   end's intensity denoise (fast_lio_sam.cpp:941-1008, 575-646, 332-365) and its parts
+* :class:`EuclideanClusterExtraction` — ``pcl::EuclideanClusterExtraction`` with one axis-aligned bounding
+  box per cluster (fast_lio_sam.cpp:343-363, post_process/clustering.py:39-75)
 
 Point records are float rows ``[x, y, z, attr...]`` (3..8 floats); PCL's
 PointXYZI is ``stride = 4``, FAST-LIO's PointXYZINormal-with-time is
@@ -137,6 +139,64 @@ def denoise_slam_map(pts, seed_thres=2800.0, cluster_seed_radius=1.0, denoise_ra
     check(lib().lio_denoise_slam_map(h._h, _fp(pts), len(pts), C.byref(p), _fp(out), C.byref(m),
                                      counts.ctypes.data_as(C.POINTER(C.c_int64))))
     return out[: m.value].copy(), counts
+
+
+class EuclideanClusterExtraction(_Handle):
+    """``pcl::EuclideanClusterExtraction``: the connected components of the graph that joins two finite points
+    closer than ``tolerance`` (strict, float squared distances), those with ``min_size <= size <= max_size``
+    kept, ordered by size descending, then by lowest member index; indices ascend inside a cluster.  The
+    defaults are PCL's (tolerance 0 — an argument error until set —, min 1, max ``INT_MAX``); the reference's
+    commented block uses 0.5, 10, 25000 (fast_lio_sam.cpp:343-363).
+    After :meth:`extract`: ``labels`` (per input point the cluster rank, -1: none), ``offsets`` / ``indices``
+    (cluster k is ``indices[offsets[k]:offsets[k + 1]]``), ``aabb`` (per cluster min x, y, z, max x, y, z:
+    post_process/clustering.py:72-75) and ``stats`` = finite points, components, accepted clusters, points in
+    them."""
+
+    def __init__(self, tolerance: float = 0.0, min_size: int = 1, max_size: int = 2**31 - 1, device: int = 0):
+        super().__init__(device)
+        self.setClusterTolerance(tolerance)
+        self.setMinClusterSize(min_size)
+        self.setMaxClusterSize(max_size)
+        self.n_clusters = 0  # accepted clusters of the last extract(), whatever its cap_clusters
+        self.labels = np.zeros(0, np.int32)
+        self.offsets = np.zeros(1, np.int64)
+        self.indices = np.zeros(0, np.int32)
+        self.aabb = np.zeros((0, 6), np.float32)
+        self.stats = np.zeros(4, np.int64)
+
+    def setClusterTolerance(self, tolerance):
+        self.tolerance = float(tolerance)
+
+    def setMinClusterSize(self, min_size):
+        self.min_size = int(min_size)
+
+    def setMaxClusterSize(self, max_size):
+        self.max_size = int(max_size)
+
+    def extract(self, pts: np.ndarray, cap_clusters: int | None = None) -> list:
+        """The list of index arrays.  ``cap_clusters`` (default: as many as there can be) bounds the clusters
+        that ``offsets`` / ``aabb`` and the returned list describe; ``labels``, ``indices`` and ``stats`` are
+        always complete."""
+        pts2 = _rows(pts)
+        n = len(pts2)
+        cap = n if cap_clusters is None else int(cap_clusters)
+        labels = np.full(n, -1, np.int32)
+        offsets = np.zeros(max(cap, 0) + 1, np.int64)
+        indices = np.zeros(n, np.int32)
+        aabb = np.zeros((max(cap, 0), 6), np.float32)
+        stats = np.zeros(4, np.int64)
+        m = C.c_int64(0)
+        i32p, i64p = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+        check(lib().lio_euclidean_clusters(self._h, _fp(pts2), n, pts2.shape[1], self.tolerance, self.min_size,
+                                           self.max_size, labels.ctypes.data_as(i32p), C.byref(m), cap,
+                                           offsets.ctypes.data_as(i64p), indices.ctypes.data_as(i32p), _fp(aabb),
+                                           stats.ctypes.data_as(i64p)))
+        k = min(m.value, cap)
+        self.n_clusters = m.value
+        self.labels, self.stats = labels, stats
+        self.offsets, self.aabb = offsets[: k + 1].copy(), aabb[:k].copy()
+        self.indices = indices[: stats[3]].copy()
+        return [self.indices[self.offsets[t]:self.offsets[t + 1]] for t in range(k)]
 
 
 def voxelize_submap(clouds, poses, voxel_res: float, handle: VoxelGrid | None = None) -> np.ndarray:

@@ -513,6 +513,32 @@ typedef struct lio_denoise_params { /* /denoise/... (fast_lio_sam.cpp:89-96, con
 int lio_denoise_slam_map(lio_filter* f, const float* pts, int64_t n, const lio_denoise_params* p, float* out,
                          int64_t* n_out, int64_t* counts5_opt);
 
+/* pcl::EuclideanClusterExtraction<PointT>::extract, PCL 1.10 [U] (clustering_and_denoise,
+ * fast_lio_sam.cpp:343-363: tolerance 0.5, min 10, max 25000), with the axis-aligned bounding box per cluster
+ * of the offline pipeline (post_process/clustering.py:39-75), restated as sets.  pts is n x stride floats
+ * (x, y, z first; stride 3..8), n < 2^31.
+ *   edge      two finite points i != j are joined when float ((dx*dx + dy*dy) + dz*dz) < r2,
+ *             r2 = (float)((double)tolerance * tolerance), strict (lio_radius_first_seed's rule);
+ *   cluster   a connected component of that graph (PCL's seed loop in index order with `processed` flags
+ *             reaches the whole component of every unprocessed seed; the points of a size-rejected
+ *             component stay processed, and max_size does not stop the growth, it only rejects);
+ *   accepted  min_size <= size <= max_size (min_size > max_size is legal: no cluster);
+ *   order     point indices ascend inside a cluster; clusters by size descending, THEN LOWEST MEMBER INDEX
+ *             ASCENDING (PCL's final sort leaves equal sizes unspecified; the index tie-break is this
+ *             library's contract);
+ *   non-finite points are in no cluster and nobody's neighbour.
+ * labels_out (n): the rank of the point's cluster in that order, -1 for non-finite points and for points of
+ * rejected components.  *n_clusters: accepted clusters.  indices_opt (n, may be NULL): all accepted points in
+ * cluster order.  offsets_opt (cap_clusters + 1, may be NULL) and aabb6_opt (6 x cap_clusters, may be NULL:
+ * float min x, y, z, max x, y, z over the members) are filled for the first min(*n_clusters, cap_clusters)
+ * clusters (offsets: one entry more, the end of the last of them); cap_clusters = 0 with NULLs is the
+ * "count only" call.  stats4_opt (may be NULL) = finite points, components, accepted clusters, points in them.
+ * LIO_ERR_ARG before any device work: tolerance non-finite or <= 0, min_size < 1, stride outside 3..8, n < 0
+ * or n >= 2^31, cap_clusters < 0, NULL n_clusters, NULL pts or labels_out with n > 0.                          */
+int lio_euclidean_clusters(lio_filter* f, const float* pts, int64_t n, int stride, float tolerance, int64_t min_size,
+                           int64_t max_size, int32_t* labels_out, int64_t* n_clusters, int64_t cap_clusters,
+                           int64_t* offsets_opt, int32_t* indices_opt, float* aabb6_opt, int64_t* stats4_opt);
+
 /* ------------------------------------------- wire / disk formats (§8(f) row 4) */
 /* One output column of a packed point record: byte offset, sensor_msgs/PointField datatype
  * (INT8 1, UINT8 2, INT16 3, UINT16 4, INT32 5, UINT32 6, FLOAT32 7, FLOAT64 8; 0 = absent -> 0)

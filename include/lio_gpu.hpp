@@ -600,6 +600,62 @@ private:
     double stats_[4] = {0, 0, 0, 0};
 };
 
+struct PointIndices {  // pcl::PointIndices without the header
+    std::vector<int> indices;
+};
+
+struct ClusterAABB {  // float min / max of x, y, z over a cluster's members (post_process/clustering.py:72-75)
+    float min[3], max[3];
+};
+
+// pcl::EuclideanClusterExtraction<PointT>: setInputCloud / setClusterTolerance / setMinClusterSize /
+// setMaxClusterSize / extract (clustering_and_denoise, fast_lio_sam.cpp:343-363).  Clusters by size descending,
+// then lowest member index (lio_gpu.h); indices ascend inside a cluster.  The defaults are PCL's: tolerance 0
+// (extract then throws the library's argument error), min 1, max INT_MAX.
+template <typename PointT>
+class EuclideanClusterExtraction {
+public:
+    explicit EuclideanClusterExtraction(FilterGPU& f) : f_(f) {}
+    void setInputCloud(const std::vector<PointT>* cloud) { in_ = cloud; }
+    void setClusterTolerance(double tolerance) { tolerance_ = tolerance; }
+    void setMinClusterSize(int min_size) { min_ = min_size; }
+    void setMaxClusterSize(int max_size) { max_ = max_size; }
+    void extract(std::vector<PointIndices>& clusters) {
+        if (!in_) throw Error(LIO_ERR_ARG, "EuclideanClusterExtraction: no input cloud");
+        const int64_t n = (int64_t)in_->size();
+        labels_.assign((size_t)n, -1);
+        std::vector<int32_t> idx((size_t)n);
+        std::vector<int64_t> off((size_t)n + 1, 0);
+        std::vector<float> box(6 * (size_t)n);
+        int64_t m = 0;
+        check(lio_euclidean_clusters(f_.handle(), reinterpret_cast<const float*>(in_->data()), n, float_stride<PointT>(),
+                                     (float)tolerance_, min_, max_, labels_.data(), &m, n, off.data(), idx.data(),
+                                     box.data(), stats_),
+              "EuclideanClusterExtraction::extract");
+        clusters.assign((size_t)m, PointIndices{});
+        aabbs_.resize((size_t)m);
+        for (int64_t k = 0; k < m; ++k) {
+            clusters[(size_t)k].indices.assign(idx.begin() + off[(size_t)k], idx.begin() + off[(size_t)k + 1]);
+            std::memcpy(&aabbs_[(size_t)k], &box[6 * (size_t)k], sizeof(ClusterAABB));
+        }
+    }
+    // of the last extract(): per input point the rank of its cluster (-1: none); one box per cluster; finite
+    // points, components, accepted clusters, points in them
+    const std::vector<int32_t>& labels() const { return labels_; }
+    const std::vector<ClusterAABB>& aabbs() const { return aabbs_; }
+    const int64_t* stats() const { return stats_; }
+
+private:
+    FilterGPU& f_;
+    const std::vector<PointT>* in_ = nullptr;
+    double tolerance_ = 0.0;  // PCL's defaults
+    int min_ = 1;
+    int max_ = 2147483647;
+    std::vector<int32_t> labels_;
+    std::vector<ClusterAABB> aabbs_;
+    int64_t stats_[4] = {0, 0, 0, 0};
+};
+
 struct DenoiseConfig {  // fast_lio_sam.h:123-129, defaults of fast_lio_sam.cpp:89-96 (config.yaml:32-42 sets 0.1, 200, 0.2)
     bool denoise_en = false;
     float seed_thres = 2800.0;
