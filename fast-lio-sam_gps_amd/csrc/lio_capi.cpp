@@ -23,6 +23,7 @@
 #include "lio_filter.hpp"
 #include "lio_denoise.hpp"
 #include "lio_cluster.hpp"
+#include "lio_plane.hpp"
 #include "lio_pool.hpp"
 #include "lio_mapupd.hpp"
 
@@ -1076,6 +1077,7 @@ struct lio_filter {
     int64_t poses_cap = 0;
     lio::DenoiseBuf dn;  // lio_sor_filter / lio_radius_first_seed / lio_denoise_slam_map
     lio::ClusterBuf cl;  // lio_euclidean_clusters (with dn: the grid, the sorts and the scan)
+    lio::PlaneBuf pl;    // lio_segment_plane (with dn: the flags and the scan)
 };
 
 static int filter_status(int rc, const char* what) {
@@ -1288,6 +1290,7 @@ int lio_filter_destroy(lio_filter* f) {
     lio::filter_free(f->b);
     lio::denoise_free(f->dn);
     lio::cluster_free(f->cl);
+    lio::plane_free(f->pl);
     for (void* q : {(void*)f->d_in, (void*)f->d_out, (void*)f->d_seg, (void*)f->d_T, (void*)f->d_poses})
         if (q) (void)hipFree(q);
     (void)hipStreamDestroy(f->st);
@@ -1447,6 +1450,72 @@ int lio_euclidean_clusters(lio_filter* f, const float* pts, int64_t n, int strid
     if (stats4_opt)
         stats4_opt[0] = cc.finite, stats4_opt[1] = cc.components, stats4_opt[2] = cc.clusters,
         stats4_opt[3] = cc.clustered_points;
+    return LIO_OK;
+}
+
+// ---- RANSAC plane segmentation (lio_plane.hip) ----
+int lio_plane_sample_triples(uint64_t seed, int64_t n, int64_t num_iterations, int32_t* out) {
+    if (n < 0 || n >= (int64_t)1 << 31 || num_iterations < 0 || num_iterations > (int64_t)1 << 20 ||
+        (n >= 3 && num_iterations > 0 && !out))
+        return fail(LIO_ERR_ARG, "lio_plane_sample_triples: bad arguments");
+    if (n >= 3) lio::plane_sample_triples(seed, n, num_iterations, out);
+    return LIO_OK;
+}
+
+int lio_segment_plane(lio_filter* f, const float* pts, int64_t n, int stride, float distance_threshold, int ransac_n,
+                      int64_t num_iterations, uint64_t seed, const int32_t* triples_opt, float* plane4_out,
+                      int64_t* best_iteration, int32_t* inliers_out, int64_t* n_inliers, uint8_t* mask_opt,
+                      int64_t* counts_opt, uint64_t* sq_opt, uint8_t* degenerate_opt, double* refit4_opt) {
+    int rc = denoise_handle(f, "lio_segment_plane");
+    if (rc) return rc;
+    const int64_t K = num_iterations;
+    const float thr2 = distance_threshold * distance_threshold;
+    if (!plane4_out || !best_iteration || !n_inliers || n < 0 || n >= (int64_t)1 << 31 || (n > 0 && (!pts || !inliers_out)) ||
+        stride < 3 || stride > lio::kMaxFields || !(distance_threshold > 0.f) || !std::isfinite(distance_threshold) ||
+        !std::isfinite(thr2) || ransac_n != 3 || K < 1 || K > (int64_t)1 << 20)
+        return fail(LIO_ERR_ARG, "lio_segment_plane: bad arguments");
+    if (triples_opt && !lio::plane_triples_valid(triples_opt, K, n))
+        return fail(LIO_ERR_ARG, "lio_segment_plane: a triple holds an index outside [0, n) or a repeated index");
+    for (int k = 0; k < 4; ++k) plane4_out[k] = 0.f;
+    *best_iteration = -1;
+    *n_inliers = 0;
+    if (refit4_opt)
+        for (int k = 0; k < 4; ++k) refit4_opt[k] = 0.0;
+    if (n < 3) {  // no hypothesis at all: every entry counts as skipped
+        if (mask_opt && n) std::memset(mask_opt, 0, (size_t)n);
+        if (counts_opt) std::memset(counts_opt, 0, (size_t)K * sizeof(int64_t));
+        if (sq_opt) std::memset(sq_opt, 0, (size_t)K * sizeof(uint64_t));
+        if (degenerate_opt) std::memset(degenerate_opt, 1, (size_t)K);
+        return LIO_OK;
+    }
+    lio::PlaneBuf& pb = f->pl;
+    if ((int64_t)pb.h_planes.size() < 4 * K) pb.h_planes.resize((size_t)(4 * K));
+    if ((int64_t)pb.h_deg.size() < K) pb.h_deg.resize((size_t)K);
+    const int32_t* tri = triples_opt;
+    if (!tri) {
+        if ((int64_t)pb.h_tri.size() < 3 * K) pb.h_tri.resize((size_t)(3 * K));
+        lio::plane_sample_triples(seed, n, K, pb.h_tri.data());
+        tri = pb.h_tri.data();
+    }
+    lio::plane_hypotheses(pts, stride, tri, K, pb.h_planes.data(), pb.h_deg.data());
+    HIP_TRY(hipSetDevice(f->dev));
+    rc = grow(&f->d_in, f->in_cap, n * stride);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(f->d_in, pts, (size_t)n * stride * sizeof(float), hipMemcpyHostToDevice, f->st));
+    lio::PlaneResult pr;
+    rc = lio::segment_plane(f->dn, pb, f->d_in, pts, n, stride, distance_threshold, K, refit4_opt != nullptr, &pr, f->st);
+    if (rc) return denoise_status(rc, "lio_segment_plane");
+    if (pr.n_inliers)
+        HIP_TRY(hipMemcpyAsync(inliers_out, pb.inliers, (size_t)pr.n_inliers * sizeof(int32_t), hipMemcpyDeviceToHost, f->st));
+    if (mask_opt) HIP_TRY(hipMemcpyAsync(mask_opt, pb.mask, (size_t)n, hipMemcpyDeviceToHost, f->st));
+    if (counts_opt) HIP_TRY(hipMemcpyAsync(counts_opt, pb.cnt, (size_t)K * sizeof(int64_t), hipMemcpyDeviceToHost, f->st));
+    if (sq_opt) HIP_TRY(hipMemcpyAsync(sq_opt, pb.sq, (size_t)K * sizeof(uint64_t), hipMemcpyDeviceToHost, f->st));
+    HIP_TRY(hipStreamSynchronize(f->st));
+    if (degenerate_opt) std::memcpy(degenerate_opt, pb.h_deg.data(), (size_t)K);
+    std::memcpy(plane4_out, pr.plane, sizeof(pr.plane));
+    *best_iteration = pr.best;
+    *n_inliers = pr.n_inliers;
+    if (refit4_opt) std::memcpy(refit4_opt, pr.refit, sizeof(pr.refit));
     return LIO_OK;
 }
 

@@ -199,6 +199,90 @@ class EuclideanClusterExtraction(_Handle):
         return [self.indices[self.offsets[t]:self.offsets[t + 1]] for t in range(k)]
 
 
+def sample_triples(seed: int, n: int, num_iterations: int) -> np.ndarray:
+    """The built-in sampler of :class:`PlaneSegmentation` (``lio_plane_sample_triples``; host only):
+    ``num_iterations`` triples of distinct indices in ``[0, n)``; none for ``n < 3``."""
+    k = int(num_iterations) if n >= 3 else 0
+    out = np.zeros((k, 3), np.int32)
+    check(lib().lio_plane_sample_triples(int(seed) & (2**64 - 1), int(n), int(num_iterations),
+                                         out.ctypes.data_as(C.POINTER(C.c_int32))))
+    return out
+
+
+class PlaneSegmentation(_Handle):
+    """Open3D's ``PointCloud.segment_plane`` as the offline pipeline calls it for ground removal
+    (post_process/clustering.py:21-28), as the contract of ``lio_segment_plane``: every one of the
+    ``num_iterations`` three-point hypotheses is scored against every point (strict float distance below
+    ``distance_threshold``), and the winner minimises (-inliers, fixed-point squared error, hypothesis index).
+    The triples come from ``triples`` (``K x 3``) or from the built-in sampler with ``seed``.
+    After :meth:`segment_plane`: ``best_iteration`` (-1: no plane), ``counts`` / ``sq`` / ``degenerate`` (per
+    hypothesis), ``mask`` (per input point) and ``refit`` (the least-squares plane through the inliers, 4
+    doubles)."""
+
+    def __init__(self, device: int = 0):
+        super().__init__(device)
+        self.best_iteration = -1
+        self.counts = np.zeros(0, np.int64)
+        self.sq = np.zeros(0, np.uint64)
+        self.degenerate = np.zeros(0, np.uint8)
+        self.mask = np.zeros(0, np.uint8)
+        self.refit = np.zeros(4, np.float64)
+
+    def segment_plane(self, pts: np.ndarray, distance_threshold: float = 0.2, ransac_n: int = 3,
+                      num_iterations: int = 1000, seed: int = 0, triples=None):
+        """``(plane4, inliers)``: float32 (a, b, c, d) and the inliers' indices ascending."""
+        pts2 = _rows(pts)
+        n, k = len(pts2), max(int(num_iterations), 0)
+        plane = np.zeros(4, np.float32)
+        inliers = np.zeros(n, np.int32)
+        counts, sq = np.zeros(k, np.int64), np.zeros(k, np.uint64)
+        degenerate, mask = np.zeros(k, np.uint8), np.zeros(n, np.uint8)
+        refit = np.zeros(4, np.float64)
+        best, m = C.c_int64(-1), C.c_int64(0)
+        tri = None
+        if triples is not None:
+            tri = np.ascontiguousarray(triples, dtype=np.int32)
+            if tri.shape != (int(num_iterations), 3):
+                raise ValueError("triples must be num_iterations x 3")
+        i32p, i64p, u8p = C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_uint8)
+        check(lib().lio_segment_plane(self._h, _fp(pts2), n, pts2.shape[1], float(distance_threshold), int(ransac_n),
+                                      int(num_iterations), int(seed) & (2**64 - 1),
+                                      tri.ctypes.data_as(i32p) if tri is not None else None, _fp(plane), C.byref(best),
+                                      inliers.ctypes.data_as(i32p), C.byref(m), mask.ctypes.data_as(u8p),
+                                      counts.ctypes.data_as(i64p), sq.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                      degenerate.ctypes.data_as(u8p), refit.ctypes.data_as(C.POINTER(C.c_double))))
+        self.best_iteration = best.value
+        self.counts, self.sq, self.degenerate, self.mask, self.refit = counts, sq, degenerate, mask, refit
+        return plane, inliers[: m.value].copy()
+
+
+def cluster_objects(pts, nb_neighbors=20, std_ratio=2.0, distance_threshold=0.2, num_iterations=1000, seed=0,
+                    tolerance=0.5, min_size=10, max_size=10000):
+    """The main block of post_process/clustering.py (:77-118) on one handle's worth of device work: statistical
+    outlier removal, ground-plane segmentation, the plane's inliers dropped, Euclidean clustering, one bounding
+    box per cluster.  Every stage is this library's (the outlier removal with PCL's semantics, the plane by the
+    contract of ``lio_segment_plane``, the clusters as PCL's).  Returns a dict: ``clusters`` (index arrays into the rows of ``pts``), ``aabb`` (per
+    cluster min x, y, z, max x, y, z), ``plane`` (a, b, c, d), ``ground`` (rows of ``pts`` on the plane) and
+    ``kept`` (rows of ``pts`` that passed the outlier removal)."""
+    pts2 = _rows(pts)
+    sor = StatisticalOutlierRemoval(nb_neighbors, std_ratio)
+    filtered = sor.filter(pts2)
+    # removed when the distance is > the threshold: the kept rows, in input order
+    kept = np.flatnonzero(~(sor.distances.astype(np.float64) > sor.stats[2])).astype(np.int64)
+    if len(kept) != len(filtered):
+        raise RuntimeError("cluster_objects: the outlier removal kept another number of rows than its distances say")
+    sor.close()
+    seg = PlaneSegmentation()
+    plane, inl = seg.segment_plane(filtered, distance_threshold, 3, num_iterations, seed)
+    seg.close()
+    rest = np.flatnonzero(seg.mask == 0) if len(filtered) else np.zeros(0, np.int64)
+    ec = EuclideanClusterExtraction(tolerance, min_size, max_size)
+    found = ec.extract(filtered[rest])
+    ec.close()
+    rows = kept[rest]
+    return dict(clusters=[rows[c] for c in found], aabb=ec.aabb, plane=plane, ground=kept[inl], kept=kept)
+
+
 def voxelize_submap(clouds, poses, voxel_res: float, handle: VoxelGrid | None = None) -> np.ndarray:
     """``voxelizePcd(sum_k transformPcd(clouds[k], poses[k]), voxel_res)``; poses are 4x4 double."""
     h = handle or VoxelGrid(voxel_res)

@@ -539,6 +539,56 @@ int lio_euclidean_clusters(lio_filter* f, const float* pts, int64_t n, int strid
                            int64_t max_size, int32_t* labels_out, int64_t* n_clusters, int64_t cap_clusters,
                            int64_t* offsets_opt, int32_t* indices_opt, float* aabb6_opt, int64_t* stats4_opt);
 
+/* RANSAC plane segmentation: Open3D's PointCloud::SegmentPlane [U] as the offline pipeline calls it for ground
+ * removal (post_process/clustering.py:21-28: distance_threshold 0.2, ransac_n 3, num_iterations 1000), restated
+ * as a contract of this library (Open3D's std::mt19937 sampling and the float sum behind its RMSE tie-break
+ * cannot be reproduced bit for bit).  pts is n x stride floats (x, y, z first; stride 3..8), 0 <= n < 2^31.
+ * All hypothesis arithmetic is float32 in the written order without contraction, division and square root
+ * correctly rounded.
+ *   hypotheses  K = num_iterations of them, 1 <= K <= 2^20; ransac_n must be 3.  The triple of hypothesis t is
+ *               triples_opt[3 t ..] (K x 3) when given, else the built-in counter-based sampler's
+ *               (lio_plane_sample_triples with `seed`).  n < 3 gives no hypothesis at all: "no plane".
+ *   plane       of (p0, p1, p2): e1 = p1 - p0, e2 = p2 - p0; (nx, ny, nz) = (e1y e2z - e1z e2y,
+ *               e1z e2x - e1x e2z, e1x e2y - e1y e2x); len = sqrtf((nx nx + ny ny) + nz nz);
+ *               (a, b, c) = (nx, ny, nz) / len; d = -((a p0x + b p0y) + c p0z).  The hypothesis is DEGENERATE,
+ *               and skipped, unless len is finite and > 0 and d is finite (collinear points, duplicates,
+ *               non-finite members).  The sign of the normal is left as computed.
+ *   score       dist_i = fabsf(((a x + b y) + c z) + d); point i is an inlier iff dist_i < distance_threshold
+ *               (strict, float: a non-finite point is never one); count = the inliers; the error is a
+ *               fixed-point sum, independent of the order of summation: thr2 = thr * thr (float, must be
+ *               finite), (m, e) = frexp(thr2), q_i = (uint64) floor((double)(float)(dist_i * dist_i) * 2^(32 - e))
+ *               (< 2^32), sq = the sum of q_i over the inliers.
+ *   winner      the non-degenerate hypothesis that minimises (-count, sq, t): Open3D ranks by fitness, then by
+ *               RMSE (for equal counts the smaller squared sum); THE LOWEST HYPOTHESIS INDEX t among equals is
+ *               this library's tie-break.  Every hypothesis degenerate, or n < 3: "no plane" — status 0,
+ *               *best_iteration = -1, no inliers, plane (0, 0, 0, 0).
+ *   departures  from Open3D: all K hypotheses are always evaluated (its `probability` early exit only drops
+ *               later hypotheses; a parallel evaluation has no use for it), and the returned inliers are
+ *               those of the winning hypothesis plane (as Open3D >= 0.13 [U]), not of the refit.
+ * plane4_out: (a, b, c, d) of the winner; *best_iteration: its t.  inliers_out (capacity n): the inliers'
+ * indices ascending, *n_inliers of them.  mask_opt (n, may be NULL): 1 for an inlier.  counts_opt (K int64) and
+ * sq_opt (K uint64), may be NULL: every hypothesis's score, 0 for a degenerate one; degenerate_opt (K, may be
+ * NULL): 1 for a degenerate one (all 1 when n < 3).  refit4_opt (4 doubles, may be NULL): the least-squares
+ * plane through the inliers (Open3D's GetPlaneFromPoints [U]) — second moments in double about the
+ * lowest-index inlier, reduced on the device in a fixed order, the eigenvector of the smallest eigenvalue of
+ * the covariance as the normal, signed so that its dot product with the winner's (a, b, c) is >= 0,
+ * d = -n . centroid; with fewer than 3 inliers the winner plane widened to double.
+ * LIO_ERR_ARG before any device work: distance_threshold <= 0, NaN or infinite (or its float square infinite),
+ * stride outside 3..8, n < 0 or n >= 2^31, num_iterations outside 1..2^20, ransac_n != 3, a triple with an
+ * index outside [0, n) or a repeated index, NULL plane4_out / best_iteration / n_inliers, NULL pts or
+ * inliers_out with n > 0.  Repeated calls give bit-identical results.                                        */
+int lio_segment_plane(lio_filter* f, const float* pts, int64_t n, int stride, float distance_threshold, int ransac_n,
+                      int64_t num_iterations, uint64_t seed, const int32_t* triples_opt, float* plane4_out,
+                      int64_t* best_iteration, int32_t* inliers_out, int64_t* n_inliers, uint8_t* mask_opt,
+                      int64_t* counts_opt, uint64_t* sq_opt, uint8_t* degenerate_opt, double* refit4_opt);
+/* The built-in sampler of lio_segment_plane, host only (no device needed): out (num_iterations x 3) = the
+ * triples of distinct indices in [0, n).  All arithmetic mod 2^64: r(c) = mix(seed + (c + 1) * 0x9E3779B97F4A7C15),
+ * mix(z): z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) * 0x94D049BB133111EB; z ^ (z >> 31)
+ * (splitmix64).  i0 = r(3t) % n; i1 = r(3t + 1) % (n - 1), + 1 if >= i0; i2 = r(3t + 2) % (n - 2), + 1 if
+ * >= min(i0, i1), then + 1 if >= max(i0, i1).  n < 3 writes nothing (status 0).  LIO_ERR_ARG: n < 0 or
+ * n >= 2^31, num_iterations < 0 or > 2^20, NULL out with something to write.                                   */
+int lio_plane_sample_triples(uint64_t seed, int64_t n, int64_t num_iterations, int32_t* out);
+
 /* ------------------------------------------- wire / disk formats (§8(f) row 4) */
 /* One output column of a packed point record: byte offset, sensor_msgs/PointField datatype
  * (INT8 1, UINT8 2, INT16 3, UINT16 4, INT32 5, UINT32 6, FLOAT32 7, FLOAT64 8; 0 = absent -> 0)

@@ -20,6 +20,7 @@
 // lio_last_error(); there is no CPU fallback behind any call.
 #pragma once
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <cmath>
 #include <cstdint>
@@ -654,6 +655,44 @@ private:
     std::vector<int32_t> labels_;
     std::vector<ClusterAABB> aabbs_;
     int64_t stats_[4] = {0, 0, 0, 0};
+};
+
+// Open3D's PointCloud::SegmentPlane as the offline pipeline calls it (post_process/clustering.py:21-28), in the
+// shape of pcl::SACSegmentation: setInputCloud / setDistanceThreshold / setMaxIterations / setSeed / segment.
+// Every hypothesis is evaluated; the winner minimises (-inliers, fixed-point squared error, hypothesis index)
+// (lio_gpu.h).  The defaults are the reference's call: 0.2, 1000 (seed 0).  No plane (every hypothesis
+// degenerate, fewer than 3 points): no inliers, coefficients 0.
+template <typename PointT>
+class PlaneSegmentation {
+public:
+    explicit PlaneSegmentation(FilterGPU& f) : f_(f) {}
+    void setInputCloud(const std::vector<PointT>* cloud) { in_ = cloud; }
+    void setDistanceThreshold(double threshold) { thr_ = threshold; }
+    void setMaxIterations(int iterations) { iters_ = iterations; }
+    void setSeed(uint64_t seed) { seed_ = seed; }
+    void segment(PointIndices& inliers, std::array<float, 4>& coefficients) {
+        if (!in_) throw Error(LIO_ERR_ARG, "PlaneSegmentation: no input cloud");
+        const int64_t n = (int64_t)in_->size();
+        std::vector<int32_t> idx((size_t)n);
+        int64_t m = 0;
+        check(lio_segment_plane(f_.handle(), reinterpret_cast<const float*>(in_->data()), n, float_stride<PointT>(),
+                                (float)thr_, 3, iters_, seed_, nullptr, coefficients.data(), &best_, idx.data(), &m,
+                                nullptr, nullptr, nullptr, nullptr, refit_),
+              "PlaneSegmentation::segment");
+        inliers.indices.assign(idx.begin(), idx.begin() + m);
+    }
+    // of the last segment(): the winning hypothesis (-1: no plane); the least-squares plane through the inliers
+    int64_t best_iteration() const { return best_; }
+    const double* refit() const { return refit_; }
+
+private:
+    FilterGPU& f_;
+    const std::vector<PointT>* in_ = nullptr;
+    double thr_ = 0.2;  // post_process/clustering.py:21-28
+    int iters_ = 1000;
+    uint64_t seed_ = 0;
+    int64_t best_ = -1;
+    double refit_[4] = {0, 0, 0, 0};
 };
 
 struct DenoiseConfig {  // fast_lio_sam.h:123-129, defaults of fast_lio_sam.cpp:89-96 (config.yaml:32-42 sets 0.1, 200, 0.2)
