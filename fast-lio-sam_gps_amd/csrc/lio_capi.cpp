@@ -26,6 +26,7 @@
 #include "lio_plane.hpp"
 #include "lio_pool.hpp"
 #include "lio_mapupd.hpp"
+#include "lio_scratch.hpp"
 
 namespace {
 
@@ -52,18 +53,22 @@ int check_device(int dev) {
     return LIO_OK;
 }
 
+static_assert(lio::kOk == LIO_OK && lio::kArg == LIO_ERR_ARG && lio::kHip == LIO_ERR_HIP && lio::kNoMem == LIO_ERR_NOMEM,
+              "the internal status codes are the public ones");
+
+// The public code and message of an internal driver's status.  arg_what: the call's wording of kArg.  Every kHip
+// has just left the failed HIP call's text in last_error() (LIO_HIP), taken here before fail() replaces it.
+int status(int rc, const char* what, const char* arg_what = "bad arguments") {
+    if (rc == lio::kOk) return LIO_OK;
+    if (rc == lio::kNoMem) return fail(LIO_ERR_NOMEM, std::string(what) + ": out of device memory");
+    if (rc == lio::kArg) return fail(LIO_ERR_ARG, std::string(what) + ": " + arg_what);
+    const std::string detail = lio::last_error();
+    return fail(LIO_ERR_HIP, std::string(what) + " failed (" + detail + ")");
+}
+
 template <class T>
 int grow(T** p, int64_t& cap, int64_t need, size_t elems_per = 1) {
-    if (need <= cap && *p) return LIO_OK;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    int64_t c = std::max<int64_t>(need, cap + cap / 2);
-    lio::count_alloc();
-    if (hipMalloc(p, (size_t)c * elems_per * sizeof(T)) != hipSuccess) {
-        cap = 0;
-        return fail(LIO_ERR_NOMEM, "hipMalloc failed");
-    }
-    cap = c;
+    if (lio::grow_buf(p, cap, need, elems_per)) return fail(LIO_ERR_NOMEM, "hipMalloc failed");
     return LIO_OK;
 }
 
@@ -275,13 +280,11 @@ int lio_map_set_params(lio_map* m, const lio_map_params* p) {
 
 static int map_build_impl(lio_map* m, const float* d_xyz, int64_t n) {
     int rc = lio::grid_build(m->grid, d_xyz, n, m->p.cell_size, m->st);
-    if (rc == -5) return fail(LIO_ERR_NOMEM, "grid build: out of device memory");
-    if (rc == -1) return fail(LIO_ERR_ARG, "grid build: invalid points (empty, too many, or non-finite)");
-    if (rc != 0) return fail(LIO_ERR_HIP, "grid build failed");
+    if (rc) return status(rc, "grid build", "invalid points (empty, too many, or non-finite)");
     // the map_incremental scratch for a scan of up to 256 k points (C3 131 k, C5 ~30 k undistorted), so the
     // stream's first update allocates nothing; larger scans grow it then
     rc = lio::mapupd_presize(m->upd, (int64_t)1 << 18, m->st);
-    if (rc) return fail(rc == -5 ? LIO_ERR_NOMEM : LIO_ERR_HIP, "map update scratch");
+    if (rc) return status(rc, "map update scratch");
     HIP_TRY(hipStreamSynchronize(m->st));
     m->n = m->grid.n;
     ++m->version;
@@ -385,13 +388,6 @@ int lio_map_gather(lio_map* m, const int32_t* ids, int64_t n, float* xyz_out) {
     return LIO_OK;
 }
 
-static int map_status(int rc, const char* what) {
-    if (rc == 0) return LIO_OK;
-    if (rc == -5) return fail(LIO_ERR_NOMEM, std::string(what) + ": out of device memory");
-    if (rc == -1) return fail(LIO_ERR_ARG, std::string(what) + ": invalid points");
-    return fail(LIO_ERR_HIP, std::string(what) + " failed");
-}
-
 int lio_map_add_device(lio_map* m, const float* d_xyz, int64_t n, int downsample, int64_t* n_added) {
     if (!m || n < 0 || (n > 0 && !d_xyz)) return fail(LIO_ERR_ARG, "lio_map_add: bad arguments");
     HIP_TRY(hipSetDevice(m->dev));
@@ -407,7 +403,7 @@ int lio_map_add_device(lio_map* m, const float* d_xyz, int64_t n, int downsample
     m->n = m->grid.n;
     ++m->version;
     if (n_added) *n_added = out[0];
-    return map_status(rc, "lio_map_add");
+    return status(rc, "lio_map_add", "invalid points");
 }
 
 int lio_map_add(lio_map* m, const float* xyz, int64_t n, int downsample, int64_t* n_added) {
@@ -432,7 +428,7 @@ int lio_map_delete_boxes(lio_map* m, const float* boxes, int nb, int64_t* n_dele
     m->n = m->grid.n;
     ++m->version;
     if (n_deleted) *n_deleted = nd;
-    return map_status(rc, "lio_map_delete_boxes");
+    return status(rc, "lio_map_delete_boxes", "invalid points");
 }
 
 // lasermap_fov_segment() [U]: float box vertices, MOV_THRESHOLD * DET_RANGE
@@ -893,7 +889,7 @@ int lio_map_incremental(lio_ctx* c, const lio_pose* pose, double filter_size_map
         st->n_skipped = out[2];
         st->n_added_downsample = out[3];
     }
-    return map_status(rc, "lio_map_incremental");
+    return status(rc, "lio_map_incremental", "invalid points");
 }
 
 int lio_get_knn(lio_ctx* c, int32_t* idx, float* d2) {
@@ -1079,13 +1075,6 @@ struct lio_filter {
     lio::ClusterBuf cl;  // lio_euclidean_clusters (with dn: the grid, the sorts and the scan)
     lio::PlaneBuf pl;    // lio_segment_plane (with dn: the flags and the scan)
 };
-
-static int filter_status(int rc, const char* what) {
-    if (rc == 0) return LIO_OK;
-    if (rc == -5) return fail(LIO_ERR_NOMEM, std::string(what) + ": out of device memory");
-    if (rc == -1) return fail(LIO_ERR_ARG, std::string(what) + ": bad arguments");
-    return fail(LIO_ERR_HIP, std::string(what) + " failed");
-}
 
 static lio::UndistortEnd undistort_end(const lio_pose* e) {
     lio::UndistortEnd u{};
@@ -1312,7 +1301,7 @@ int lio_voxel_grid(lio_filter* f, const float* pts, int64_t n, int stride, const
     HIP_TRY(hipMemcpyAsync(f->d_in, pts, (size_t)n * stride * sizeof(float), hipMemcpyHostToDevice, f->st));
     int64_t m = 0;
     rc = lio::voxel_grid(f->b, f->d_in, n, stride, leaf, f->d_out, &m, f->st);
-    if (rc) return filter_status(rc, "lio_voxel_grid");
+    if (rc) return status(rc, "lio_voxel_grid");
     if (m) HIP_TRY(hipMemcpyAsync(out, f->d_out, (size_t)m * stride * sizeof(float), hipMemcpyDeviceToHost, f->st));
     HIP_TRY(hipStreamSynchronize(f->st));
     *n_out = m;
@@ -1326,14 +1315,6 @@ static int denoise_handle(lio_filter* f, const char* what) {
     const int rc = check_device(0);
     if (rc) return rc;
     return fail(LIO_ERR_ARG, std::string(what) + ": handle is NULL");
-}
-
-// status of a lio_denoise.hip driver: every -2 it returns has just left the failed HIP call's text in
-// last_error() (its DCHK), taken here before fail() replaces it
-static int denoise_status(int rc, const char* what) {
-    if (rc != -2) return filter_status(rc, what);
-    const std::string detail = lio::last_error();
-    return fail(LIO_ERR_HIP, std::string(what) + " failed (" + detail + ")");
 }
 
 int lio_sor_filter(lio_filter* f, const float* pts, int64_t n, int stride, int mean_k, double stddev_mul, int negative,
@@ -1354,7 +1335,7 @@ int lio_sor_filter(lio_filter* f, const float* pts, int64_t n, int stride, int m
     int64_t m = 0;
     rc = lio::sor_filter(f->dn, f->d_in, n, stride, mean_k, stddev_mul, negative != 0, f->d_out, &m, distances_opt,
                          stats4_opt, f->st);
-    if (rc) return denoise_status(rc, "lio_sor_filter");
+    if (rc) return status(rc, "lio_sor_filter");
     if (m) HIP_TRY(hipMemcpyAsync(out, f->d_out, (size_t)m * stride * sizeof(float), hipMemcpyDeviceToHost, f->st));
     HIP_TRY(hipStreamSynchronize(f->st));
     *n_out = m;
@@ -1374,12 +1355,12 @@ int lio_radius_first_seed(lio_filter* f, const float* pts, int64_t n, int stride
     rc = grow(&f->d_in, f->in_cap, n * stride);
     if (rc) return rc;
     rc = lio::denoise_reserve(f->dn, std::max(n, ns));
-    if (rc) return denoise_status(rc, "lio_radius_first_seed");
+    if (rc) return status(rc, "lio_radius_first_seed");
     HIP_TRY(hipMemcpyAsync(f->d_in, pts, (size_t)n * stride * sizeof(float), hipMemcpyHostToDevice, f->st));
     if (ns) HIP_TRY(hipMemcpyAsync(f->dn.seeds_xyz, seeds_xyz, (size_t)ns * 3 * sizeof(float), hipMemcpyHostToDevice, f->st));
     rc = lio::radius_first_seed(f->dn, f->d_in, n, stride, f->dn.seeds_xyz, ns, radius, f->dn.seed_id, f->dn.seed_d2,
                                 f->st);
-    if (rc) return denoise_status(rc, "lio_radius_first_seed");
+    if (rc) return status(rc, "lio_radius_first_seed");
     HIP_TRY(hipMemcpyAsync(seed_out, f->dn.seed_id, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, f->st));
     if (d2_out_opt)
         HIP_TRY(hipMemcpyAsync(d2_out_opt, f->dn.seed_d2, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, f->st));
@@ -1408,7 +1389,7 @@ int lio_denoise_slam_map(lio_filter* f, const float* pts, int64_t n, const lio_d
                                 p->noise_thres, p->mean_k,              p->stddev_mul};
     int64_t m = 0;
     rc = lio::denoise_slam_map(f->dn, f->d_in, n, dp, f->d_out, &m, counts5_opt, f->st);
-    if (rc) return denoise_status(rc, "lio_denoise_slam_map");
+    if (rc) return status(rc, "lio_denoise_slam_map");
     if (m) HIP_TRY(hipMemcpyAsync(out, f->d_out, (size_t)m * 4 * sizeof(float), hipMemcpyDeviceToHost, f->st));
     HIP_TRY(hipStreamSynchronize(f->st));
     *n_out = m;
@@ -1435,7 +1416,7 @@ int lio_euclidean_clusters(lio_filter* f, const float* pts, int64_t n, int strid
     HIP_TRY(hipMemcpyAsync(f->d_in, pts, (size_t)n * stride * sizeof(float), hipMemcpyHostToDevice, f->st));
     lio::ClusterCounts cc;
     rc = lio::euclidean_clusters(f->dn, f->cl, f->d_in, n, stride, tolerance, min_size, max_size, cap_clusters, &cc, f->st);
-    if (rc) return denoise_status(rc, "lio_euclidean_clusters");
+    if (rc) return status(rc, "lio_euclidean_clusters");
     const int64_t m = std::min(cc.clusters, cap_clusters);
     HIP_TRY(hipMemcpyAsync(labels_out, f->cl.labels, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, f->st));
     if (indices_opt && cc.clustered_points)
@@ -1504,7 +1485,7 @@ int lio_segment_plane(lio_filter* f, const float* pts, int64_t n, int stride, fl
     HIP_TRY(hipMemcpyAsync(f->d_in, pts, (size_t)n * stride * sizeof(float), hipMemcpyHostToDevice, f->st));
     lio::PlaneResult pr;
     rc = lio::segment_plane(f->dn, pb, f->d_in, pts, n, stride, distance_threshold, K, refit4_opt != nullptr, &pr, f->st);
-    if (rc) return denoise_status(rc, "lio_segment_plane");
+    if (rc) return status(rc, "lio_segment_plane");
     if (pr.n_inliers)
         HIP_TRY(hipMemcpyAsync(inliers_out, pb.inliers, (size_t)pr.n_inliers * sizeof(int32_t), hipMemcpyDeviceToHost, f->st));
     if (mask_opt) HIP_TRY(hipMemcpyAsync(mask_opt, pb.mask, (size_t)n, hipMemcpyDeviceToHost, f->st));
@@ -1547,11 +1528,11 @@ int lio_submap_voxelize(lio_filter* f, const float* pts, const int64_t* seg_off,
     HIP_TRY(hipMemcpyAsync(f->d_T, poses16, (size_t)nk * 16 * sizeof(double), hipMemcpyHostToDevice, f->st));
     float* d_tf = f->d_out + (size_t)n * stride;  // transformed, concatenated cloud
     rc = lio::transform_segments(f->d_in, n, stride, f->d_seg, nk, f->d_T, d_tf, f->st);
-    if (rc) return filter_status(rc, "lio_submap_voxelize");
+    if (rc) return status(rc, "lio_submap_voxelize");
     const float leaf[3] = {voxel_res, voxel_res, voxel_res};
     int64_t m = 0;
     rc = lio::voxel_grid(f->b, d_tf, n, stride, leaf, f->d_out, &m, f->st);
-    if (rc) return filter_status(rc, "lio_submap_voxelize");
+    if (rc) return status(rc, "lio_submap_voxelize");
     if (m) HIP_TRY(hipMemcpyAsync(out, f->d_out, (size_t)m * stride * sizeof(float), hipMemcpyDeviceToHost, f->st));
     HIP_TRY(hipStreamSynchronize(f->st));
     *n_out = m;
@@ -1602,7 +1583,7 @@ int lio_preprocess(lio_filter* f, const float* raw, int64_t n, int stride, const
     if (rc == 2) rc = -2;
     if (rc < 0) {
         (void)hipStreamSynchronize(st);  // the staging buffer is reused by the next call
-        return filter_status(rc, "lio_preprocess");
+        return status(rc, "lio_preprocess");
     }
     if (m) HIP_TRY(hipMemcpyAsync(out, f->d_out, (size_t)m * stride * sizeof(float), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -1640,9 +1621,9 @@ static int scan_prep_device(lio_ctx* c, int64_t rows, int stride, const lio::Sca
         rc = lio::scan_preprocess_enqueue(c->filt, c->d_raw, rows, stride, sp, d_poses, n_poses,
                                           undistort_end(end), c->d_rec, st, presel, vox ? c->d_body : nullptr,
                                           vox ? c->d_sel : nullptr, rp);
-        if (rc) return bail(filter_status(rc, what));
+        if (rc) return bail(status(rc, what));
         if (!vox) rc = lio::records_to_xyz_sel(c->d_rec, rows, stride, c->d_body, c->d_sel, st);
-        if (rc) return bail(filter_status(rc, what));
+        if (rc) return bail(status(rc, what));
         const auto tw = std::chrono::steady_clock::now();
         rc = lio::scan_preprocess_finish(c->filt, stride, c->d_rec, &m, &mu, st);
         if (prep_profile())
@@ -1650,10 +1631,10 @@ static int scan_prep_device(lio_ctx* c, int64_t rows, int stride, const lio::Sca
                          attempt);
     }
     if (rc == 2) rc = -2;
-    if (rc < 0) return bail(filter_status(rc, what));
+    if (rc < 0) return bail(status(rc, what));
     if (rc == 1) {  // VoxelGrid index overflow: the output is the undistorted input, its xyz again
         rc = lio::records_to_xyz_sel(c->d_rec, m, stride, c->d_body, c->d_sel, st);
-        if (rc) return bail(filter_status(rc, what));
+        if (rc) return bail(status(rc, what));
         HIP_TRY(hipStreamSynchronize(st));
     }
     c->n = m;
@@ -1758,7 +1739,7 @@ int lio_cloud2_decode(lio_filter* f, const uint8_t* data, int64_t n_points, int3
     HIP_TRY(hipMemcpyAsync(f->d_in, data, (size_t)bytes, hipMemcpyHostToDevice, f->st));
     rc = lio::cloud_decode(reinterpret_cast<const uint8_t*>(f->d_in), n_points, point_step, is_bigendian != 0,
                            reinterpret_cast<const lio::CloudField*>(fields), n_fields, f->d_out, f->st);
-    if (rc) return filter_status(rc, "lio_cloud2_decode");
+    if (rc) return status(rc, "lio_cloud2_decode");
     HIP_TRY(hipMemcpyAsync(out, f->d_out, (size_t)n_points * n_fields * sizeof(float), hipMemcpyDeviceToHost, f->st));
     HIP_TRY(hipStreamSynchronize(f->st));
     return LIO_OK;
@@ -1781,7 +1762,7 @@ int lio_cloud2_encode(lio_filter* f, const float* rec, int64_t n, int stride, co
     HIP_TRY(hipMemcpyAsync(f->d_in, rec, (size_t)n * stride * sizeof(float), hipMemcpyHostToDevice, f->st));
     rc = lio::cloud_encode(f->d_in, n, stride, point_step, reinterpret_cast<const lio::CloudField*>(fields), n_fields,
                            reinterpret_cast<uint8_t*>(f->d_out), f->st);
-    if (rc) return filter_status(rc, "lio_cloud2_encode");
+    if (rc) return status(rc, "lio_cloud2_encode");
     HIP_TRY(hipMemcpyAsync(data, f->d_out, (size_t)bytes, hipMemcpyDeviceToHost, f->st));
     HIP_TRY(hipStreamSynchronize(f->st));
     return LIO_OK;
@@ -1820,7 +1801,7 @@ int lio_scan_preprocess_cloud2(lio_ctx* c, const uint8_t* data, int64_t n_points
                            reinterpret_cast<const lio::CloudField*>(fields), 5, c->d_raw, st);
     if (rc) {
         (void)hipStreamSynchronize(st);
-        return filter_status(rc, "lio_scan_preprocess_cloud2");
+        return status(rc, "lio_scan_preprocess_cloud2");
     }
     return scan_prep_device(c, rows, 5, sp, n_poses, end, n_down, "lio_scan_preprocess_cloud2");
 }

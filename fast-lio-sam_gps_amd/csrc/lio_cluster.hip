@@ -22,28 +22,16 @@
 // key that orders clusters of equal size.  Everything after is sorts, scans and min / max.
 #include <algorithm>
 #include <cmath>
-#include <string>
 
 #include "lio_dev.hpp"
-#include "lio_error.hpp"
+#include "lio_scratch.hpp"
 #include "lio_cluster.hpp"
 
 namespace lio {
 
 namespace {
 
-#define CCHK(x)                                                                    \
-    do {                                                                           \
-        const hipError_t e_ = (x);                                                 \
-        if (e_ != hipSuccess) {                                                    \
-            last_error() = std::string(#x) + ": " + hipGetErrorString(e_);         \
-            return -2;                                                             \
-        }                                                                          \
-    } while (0)
-
 constexpr uint32_t kNoRun = 0xffffffffu;
-
-inline int nblk(int64_t n) { return (int)std::max<int64_t>(1, (n + 255) / 256); }
 
 __global__ void cl_init_kernel(uint32_t* __restrict__ parent, int64_t n) {
     const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
@@ -291,37 +279,31 @@ __global__ void __launch_bounds__(256) cl_aabb_kernel(const float* __restrict__ 
 }
 
 int cluster_reserve(ClusterBuf& c, int64_t n) {
-    if (n <= c.cap && c.arena) return 0;
-    const int64_t cap = std::min<int64_t>(std::max<int64_t>(std::max<int64_t>(n, c.cap + c.cap / 2), 4096), 0x7fffff00);
-    if (c.arena) (void)hipFree(c.arena);
-    c = ClusterBuf{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = off;
-        off += (bytes + 255) & ~(size_t)255;
-        return at;
-    };
+    if (n <= c.cap && c.arena) return kOk;
+    const int64_t cap = std::min<int64_t>(grown<int64_t>(n, c.cap, 4096), 0x7fffff00);
+    dev_free(&c.arena);
+    c.cap = 0;
     const size_t C = (size_t)cap;
-    const size_t o_parent = take(4 * C), o_run_of = take(4 * C), o_run_start = take(4 * (C + 1)), o_rank_of = take(4 * C);
-    const size_t o_labels = take(4 * C), o_indices = take(4 * C), o_offsets = take(8 * (C + 1)), o_aabb = take(24 * C);
-    const size_t o_cnt = take(64);
+    auto carve = [&](Carver at) {  // the arena's fields, once each, in arena order
+        at(c.parent, C), at(c.run_of, C), at(c.run_start, C + 1), at(c.rank_of, C);
+        at(c.labels, C), at(c.indices, C), at(c.offsets, C + 1), at(c.aabb, 6 * C), at(c.cnt, 16);
+        return at.bytes();
+    };
+    const size_t total = carve(Carver{});
     count_alloc();
-    if (hipMalloc(&c.arena, off) != hipSuccess) {
+    if (hipMalloc(&c.arena, total) != hipSuccess) {
         c.arena = nullptr;
-        return -5;
+        return kNoMem;
     }
-    auto* a = static_cast<uint8_t*>(c.arena);
-    c.parent = (uint32_t*)(a + o_parent), c.run_of = (uint32_t*)(a + o_run_of), c.run_start = (uint32_t*)(a + o_run_start);
-    c.rank_of = (int32_t*)(a + o_rank_of), c.labels = (int32_t*)(a + o_labels), c.indices = (int32_t*)(a + o_indices);
-    c.offsets = (int64_t*)(a + o_offsets), c.aabb = (float*)(a + o_aabb), c.cnt = (uint32_t*)(a + o_cnt);
+    carve(Carver{c.arena});
     c.cap = cap;
-    return 0;
+    return kOk;
 }
 
 }  // namespace
 
 void cluster_free(ClusterBuf& c) {
-    if (c.arena) (void)hipFree(c.arena);
+    dev_free(&c.arena);
     c = ClusterBuf{};
 }
 
@@ -330,12 +312,12 @@ int euclidean_clusters(DenoiseBuf& b, ClusterBuf& c, const float* d_pts, int64_t
     *counts = ClusterCounts{};
     if (n <= 0) return 0;
     if (stride < 3 || stride > 8 || !(tolerance > 0.f) || !std::isfinite(tolerance) || min_size < 1 || cap_clusters < 0)
-        return -1;
+        return kArg;
     int rc = denoise_reserve(b, n);
     if (!rc) rc = cluster_reserve(c, n);
     if (rc) return rc;
     const float r2 = (float)((double)tolerance * (double)tolerance);  // PCL passes the tolerance, FLANN squares it [U]
-    CCHK(hipMemsetAsync(c.cnt, 0, 64, st));
+    LIO_HIP(hipMemsetAsync(c.cnt, 0, 64, st));
     if ((rc = dn_build_grid(b, d_pts, n, stride, 0.f, tolerance * 1.001f, st))) return rc;
     cl_init_kernel<<<nblk(n), 256, 0, st>>>(c.parent, n);
     cl_union_kernel<<<nblk(n), 256, 0, st>>>(b.g4, b.start, b.geom, n, tolerance, r2, c.parent);
@@ -350,11 +332,11 @@ int euclidean_clusters(DenoiseBuf& b, ClusterBuf& c, const float* d_pts, int64_t
         if ((rc = dn_sort64(b, ncomp, 64, st))) return rc;
         cl_rank_kernel<<<nblk(ncomp + 1), 256, 0, st>>>(b.k64_alt, b.idx_alt, ncomp, c.rank_of, b.flags, c.cnt);
     }
-    CCHK(hipMemcpyAsync(b.h_cnt + 2, c.cnt, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    LIO_HIP(hipMemcpyAsync(b.h_cnt + 2, c.cnt, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     if (ncomp > 0) {
         if ((rc = dn_scan_count(b, ncomp, &npts, st))) return rc;  // b.pos[t] = offset of cluster t
     } else {
-        CCHK(hipStreamSynchronize(st));  // b.pos[0] = 0 from the first scan
+        LIO_HIP(hipStreamSynchronize(st));  // b.pos[0] = 0 from the first scan
     }
     counts->finite = b.h_cnt[2];
     counts->components = ncomp;
@@ -364,7 +346,7 @@ int euclidean_clusters(DenoiseBuf& b, ClusterBuf& c, const float* d_pts, int64_t
     const int64_t m = std::min(counts->clusters, cap_clusters);
     cl_offsets_kernel<<<nblk(m + 1), 256, 0, st>>>(b.pos, m, c.offsets);
     if (m > 0) cl_aabb_kernel<<<(unsigned)((m + 3) / 4), 256, 0, st>>>(d_pts, stride, c.indices, b.pos, m, c.aabb);
-    CCHK(hipGetLastError());
+    LIO_HIP(hipGetLastError());
     return 0;
 }
 

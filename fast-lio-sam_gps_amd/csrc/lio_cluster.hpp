@@ -34,7 +34,7 @@ void cluster_free(ClusterBuf& c);
 // (the accepted points in cluster order), and for the first min(clusters, cap_clusters) clusters c.offsets
 // (+ 1 entry) and c.aabb; the counts on the host.  Waits for the stream twice (the component count, then the
 // cluster count: two words each); the results are complete when the stream has drained.
-// Status: 0, -1 bad arguments, -2 HIP error (text in last_error()), -5 out of memory.
+// Status (lio_scratch.hpp): kOk, kArg bad arguments, kHip (text in last_error()), kNoMem.
 int euclidean_clusters(DenoiseBuf& b, ClusterBuf& c, const float* d_pts, int64_t n, int stride, float tolerance,
                        int64_t min_size, int64_t max_size, int64_t cap_clusters, ClusterCounts* counts, hipStream_t st);
 

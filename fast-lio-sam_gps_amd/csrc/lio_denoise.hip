@@ -16,15 +16,12 @@
 // (non-decreasing) function of the coordinate — float subtraction of a constant, multiplication by a positive
 // constant, floor and clamping all are.  Squared distances are sqdist3's float ((dx*dx + dy*dy) + dz*dz),
 // the expression the ICP 1-NN uses for FLANN's L2 (-ffp-contract=off: no FMA).
-#include <hipcub/hipcub.hpp>
-
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <string>
 
 #include "lio_dev.hpp"
-#include "lio_error.hpp"
+#include "lio_scratch_cub.hpp"
 #include "lio_denoise.hpp"
 
 namespace lio {
@@ -34,19 +31,6 @@ namespace {
 constexpr int kDnPartBlocks = 1024;  // AABB partials
 constexpr int kCand = 1024;          // candidate squared distances a query's wave holds in LDS
 constexpr int kMaxMeanK = 255;
-
-// a failed HIP call leaves its text in last_error(); the denoise entry points' status message appends it
-// (lio_capi.cpp denoise_status)
-#define DCHK(x)                                                                    \
-    do {                                                                           \
-        const hipError_t e_ = (x);                                                 \
-        if (e_ != hipSuccess) {                                                    \
-            last_error() = std::string(#x) + ": " + hipGetErrorString(e_);         \
-            return -2;                                                             \
-        }                                                                          \
-    } while (0)
-
-inline int nblk(int64_t n) { return (int)std::max<int64_t>(1, (n + 255) / 256); }
 
 // per block: min / max of the finite points it covers -> part[6 blockIdx.x ..] (lo xyz, hi xyz)
 __device__ __forceinline__ void block_minmax6(float (*s)[256], const float* lo, const float* hi) {
@@ -467,41 +451,19 @@ __global__ void gather_rows4_kernel(const float* __restrict__ in, const uint32_t
 
 // ---- host side (dn_*: shared with lio_cluster.hip through lio_denoise.hpp) ------------------------------
 int dn_sort32(DenoiseBuf& b, int64_t n, int bits, hipStream_t st) {
-    size_t bytes = 0;
-    DCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, b.keys, b.keys_alt, b.vals, b.vals_alt, (int)n, 0, bits, st));
-    if (bytes > b.tmp_bytes) {
-        last_error() = "denoise scratch smaller than the sort / scan needs";
-        return -2;
-    }
-    bytes = b.tmp_bytes;
-    DCHK(hipcub::DeviceRadixSort::SortPairs(b.tmp, bytes, b.keys, b.keys_alt, b.vals, b.vals_alt, (int)n, 0, bits, st));
-    return 0;
+    return cub_sort_pairs(b.tmp, b.tmp_bytes, kFixedScratch, b.keys, b.keys_alt, b.vals, b.vals_alt, n, bits, st);
 }
 
 int dn_sort64(DenoiseBuf& b, int64_t n, int bits, hipStream_t st) {
-    size_t bytes = 0;
-    DCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, b.k64, b.k64_alt, b.idx, b.idx_alt, (int)n, 0, bits, st));
-    if (bytes > b.tmp_bytes) {
-        last_error() = "denoise scratch smaller than the sort / scan needs";
-        return -2;
-    }
-    bytes = b.tmp_bytes;
-    DCHK(hipcub::DeviceRadixSort::SortPairs(b.tmp, bytes, b.k64, b.k64_alt, b.idx, b.idx_alt, (int)n, 0, bits, st));
-    return 0;
+    return cub_sort_pairs(b.tmp, b.tmp_bytes, kFixedScratch, b.k64, b.k64_alt, b.idx, b.idx_alt, n, bits, st);
 }
 
 // pos = exclusive scan of flags[0 .. n]; *count = pos[n].  Waits for the stream.
 int dn_scan_count(DenoiseBuf& b, int64_t n, int64_t* count, hipStream_t st) {
-    size_t bytes = 0;
-    DCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, b.flags, b.pos, (int)(n + 1), st));
-    if (bytes > b.tmp_bytes) {
-        last_error() = "denoise scratch smaller than the sort / scan needs";
-        return -2;
-    }
-    bytes = b.tmp_bytes;
-    DCHK(hipcub::DeviceScan::ExclusiveSum(b.tmp, bytes, b.flags, b.pos, (int)(n + 1), st));
-    DCHK(hipMemcpyAsync(b.h_cnt, b.pos + n, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    DCHK(hipStreamSynchronize(st));
+    const int rc = cub_exclusive_sum(b.tmp, b.tmp_bytes, kFixedScratch, b.flags, b.pos, n + 1, st);
+    if (rc) return rc;
+    LIO_HIP(hipMemcpyAsync(b.h_cnt, b.pos + n, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    LIO_HIP(hipStreamSynchronize(st));
     *count = b.h_cnt[0];
     return 0;
 }
@@ -524,7 +486,7 @@ int dn_build_grid(DenoiseBuf& b, const float* d_pts, int64_t n, int stride, floa
     if (rc) return rc;
     dn_start_kernel<<<nblk((int64_t)cells_cap + 1), 256, 0, st>>>(b.keys_alt, n, cells_cap, b.start);
     dn_gather_kernel<<<nblk(n), 256, 0, st>>>(d_pts, n, stride, b.vals_alt, b.g4);
-    DCHK(hipGetLastError());
+    LIO_HIP(hipGetLastError());
     return 0;
 }
 
@@ -536,73 +498,62 @@ void denoise_free(DenoiseBuf& b) {
 }
 
 int denoise_reserve(DenoiseBuf& b, int64_t n) {
-    if (n >= (int64_t)0x7fffff00) return -1;
-    if (n <= b.cap && b.arena) return 0;
-    const int64_t c = std::min<int64_t>(std::max<int64_t>(std::max<int64_t>(n, b.cap + b.cap / 2), 4096), 0x7fffff00);
-    if (b.arena) (void)hipFree(b.arena);
+    if (n >= (int64_t)0x7fffff00) return kArg;
+    if (n <= b.cap && b.arena) return kOk;
+    const int64_t c = std::min<int64_t>(grown<int64_t>(n, b.cap, 4096), 0x7fffff00);
+    dev_free(&b.arena);
     if (b.h_dist) (void)hipHostFree(b.h_dist);
-    b.arena = nullptr, b.h_dist = nullptr, b.cap = 0;
+    b.h_dist = nullptr, b.cap = 0;
     if (!b.h_cnt) {
         count_alloc();
-        if (hipHostMalloc(&b.h_cnt, 64) != hipSuccess) return -5;
+        if (hipHostMalloc(&b.h_cnt, 64) != hipSuccess) return kNoMem;
     }
     // the sort / scan scratch for the whole capacity, so a call up to it never allocates
     size_t s32 = 0, s64 = 0, sx = 0;
-    DCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, s32, b.keys, b.keys_alt, b.vals, b.vals_alt, (int)c, 0, 32));
-    DCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, s64, b.k64, b.k64_alt, b.idx, b.idx_alt, (int)c, 0, 64));
-    DCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, sx, b.flags, b.pos, (int)(c + 1)));
+    LIO_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, s32, b.keys, b.keys_alt, b.vals, b.vals_alt, (int)c, 0, 32));
+    LIO_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, s64, b.k64, b.k64_alt, b.idx, b.idx_alt, (int)c, 0, 64));
+    LIO_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, sx, b.flags, b.pos, (int)(c + 1)));
     const size_t tmp = std::max(std::max(s32, s64), sx) + 256;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = off;
-        off += (bytes + 255) & ~(size_t)255;
-        return at;
-    };
     const size_t C = (size_t)c;
-    const size_t o_keys = take(4 * C), o_keys_alt = take(4 * C), o_vals = take(4 * C), o_vals_alt = take(4 * C);
-    const size_t o_start = take(4 * (C + 66)), o_g4 = take(16 * C), o_part = take(4 * 6 * kDnPartBlocks);
-    const size_t o_geom = take(sizeof(DnGeom)), o_dist = take(4 * C), o_flags = take(4 * (C + 1)), o_pos = take(4 * (C + 1));
-    const size_t o_sxyz = take(12 * C), o_sid = take(4 * C), o_sd2 = take(4 * C), o_idx = take(4 * C), o_idx_alt = take(4 * C);
-    const size_t o_k64 = take(8 * C), o_k64_alt = take(8 * C), o_ca = take(16 * C), o_cb = take(16 * C), o_tmp = take(tmp);
+    auto carve = [&](Carver at) {  // the arena's fields, once each, in arena order
+        at(b.keys, C), at(b.keys_alt, C), at(b.vals, C), at(b.vals_alt, C);
+        at(b.start, C + 66), at(b.g4, C), at(b.part, 6 * kDnPartBlocks), at(b.geom, 1);
+        at(b.dist, C), at(b.flags, C + 1), at(b.pos, C + 1);
+        at(b.seeds_xyz, 3 * C), at(b.seed_id, C), at(b.seed_d2, C), at(b.idx, C), at(b.idx_alt, C);
+        at(b.k64, C), at(b.k64_alt, C), at(b.cloud_a, 4 * C), at(b.cloud_b, 4 * C), at(b.tmp, tmp);
+        return at.bytes();
+    };
+    const size_t total = carve(Carver{});
     count_alloc(2);
-    if (hipMalloc(&b.arena, off) != hipSuccess || hipHostMalloc(&b.h_dist, C * sizeof(float)) != hipSuccess) {
-        if (b.arena) (void)hipFree(b.arena);
-        b.arena = nullptr;
-        return -5;
+    if (hipMalloc(&b.arena, total) != hipSuccess || hipHostMalloc(&b.h_dist, C * sizeof(float)) != hipSuccess) {
+        dev_free(&b.arena);
+        b.h_dist = nullptr;
+        return kNoMem;
     }
-    auto* a = static_cast<uint8_t*>(b.arena);
-    b.arena_bytes = off;
-    b.keys = (uint32_t*)(a + o_keys), b.keys_alt = (uint32_t*)(a + o_keys_alt);
-    b.vals = (uint32_t*)(a + o_vals), b.vals_alt = (uint32_t*)(a + o_vals_alt);
-    b.start = (uint32_t*)(a + o_start), b.g4 = (float4*)(a + o_g4), b.part = (float*)(a + o_part);
-    b.geom = (DnGeom*)(a + o_geom), b.dist = (float*)(a + o_dist);
-    b.flags = (uint32_t*)(a + o_flags), b.pos = (uint32_t*)(a + o_pos);
-    b.seeds_xyz = (float*)(a + o_sxyz), b.seed_id = (int32_t*)(a + o_sid), b.seed_d2 = (float*)(a + o_sd2);
-    b.idx = (uint32_t*)(a + o_idx), b.idx_alt = (uint32_t*)(a + o_idx_alt);
-    b.k64 = (uint64_t*)(a + o_k64), b.k64_alt = (uint64_t*)(a + o_k64_alt);
-    b.cloud_a = (float*)(a + o_ca), b.cloud_b = (float*)(a + o_cb);
-    b.tmp = a + o_tmp, b.tmp_bytes = tmp;
+    carve(Carver{b.arena});
+    b.arena_bytes = total;
+    b.tmp_bytes = tmp;
     b.h_cap = c;
     b.cap = c;
-    return 0;
+    return kOk;
 }
 
 int sor_distances(DenoiseBuf& b, const float* d_pts, int64_t n, int stride, int mean_k, float* d_dist, hipStream_t st) {
     if (n <= 0) return 0;
-    if (stride < 3 || stride > 8 || mean_k < 1 || mean_k > kMaxMeanK) return -1;
+    if (stride < 3 || stride > 8 || mean_k < 1 || mean_k > kMaxMeanK) return kArg;
     int rc = denoise_reserve(b, n);
     if (rc) return rc;
     rc = dn_build_grid(b, d_pts, n, stride, (float)(mean_k + 1), 0.f, st);
     if (rc) return rc;
     sor_knn_kernel<<<(unsigned)n, 64, 0, st>>>(b.g4, b.start, b.geom, n, mean_k, d_dist);
-    DCHK(hipGetLastError());
+    LIO_HIP(hipGetLastError());
     return 0;
 }
 
 int sor_filter(DenoiseBuf& b, const float* d_pts, int64_t n, int stride, int mean_k, double stddev_mul, bool negative,
                float* d_out, int64_t* n_out, float* h_dist_out, double* stats4, hipStream_t st) {
     *n_out = 0;
-    if (stride < 3 || stride > 8 || mean_k < 1 || mean_k > kMaxMeanK) return -1;
+    if (stride < 3 || stride > 8 || mean_k < 1 || mean_k > kMaxMeanK) return kArg;
     double sum = 0.0, sq_sum = 0.0;
     int64_t nv = 0;
     if (n > 0) {
@@ -610,8 +561,8 @@ int sor_filter(DenoiseBuf& b, const float* d_pts, int64_t n, int stride, int mea
         if (rc) return rc;
         rc = sor_distances(b, d_pts, n, stride, mean_k, b.dist, st);
         if (rc) return rc;
-        DCHK(hipMemcpyAsync(b.h_dist, b.dist, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, st));
-        DCHK(hipStreamSynchronize(st));
+        LIO_HIP(hipMemcpyAsync(b.h_dist, b.dist, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, st));
+        LIO_HIP(hipStreamSynchronize(st));
         // PCL's loop [U], in index order: the float product d * d is promoted, the sums are double
         for (int64_t i = 0; i < n; ++i) {
             float d = b.h_dist[i];
@@ -634,26 +585,26 @@ int sor_filter(DenoiseBuf& b, const float* d_pts, int64_t n, int stride, int mea
     const int rc = dn_scan_count(b, n, n_out, st);
     if (rc) return rc;
     scatter_rows_kernel<<<nblk(n), 256, 0, st>>>(d_pts, n, stride, stride, b.flags, b.pos, d_out);
-    DCHK(hipGetLastError());
+    LIO_HIP(hipGetLastError());
     return 0;
 }
 
 int radius_first_seed(DenoiseBuf& b, const float* d_pts, int64_t n, int stride, const float* d_seeds_xyz, int64_t ns,
                       float radius, int32_t* d_seed, float* d_d2, hipStream_t st) {
     if (n <= 0) return 0;
-    if (stride < 3 || stride > 8 || ns < 0 || !(radius >= 0.f) || !std::isfinite(radius)) return -1;
+    if (stride < 3 || stride > 8 || ns < 0 || !(radius >= 0.f) || !std::isfinite(radius)) return kArg;
     int rc = denoise_reserve(b, std::max(n, ns));
     if (rc) return rc;
     if (ns == 0) {
         no_seed_kernel<<<nblk(n), 256, 0, st>>>(n, d_seed, d_d2);
-        DCHK(hipGetLastError());
+        LIO_HIP(hipGetLastError());
         return 0;
     }
     rc = dn_build_grid(b, d_seeds_xyz, ns, 3, 0.f, radius > 0.f ? radius : 1.f, st);
     if (rc) return rc;
     const float r2 = (float)((double)radius * (double)radius);  // PCL passes radius * radius cast to float [U]
     radius_seed_kernel<<<nblk(n), 256, 0, st>>>(d_pts, n, stride, b.g4, b.start, b.geom, radius, r2, d_seed, d_d2);
-    DCHK(hipGetLastError());
+    LIO_HIP(hipGetLastError());
     return 0;
 }
 
@@ -664,7 +615,7 @@ int denoise_slam_map(DenoiseBuf& b, const float* d_pts, int64_t n, const Denoise
     if (counts5) std::memcpy(counts5, cnt, sizeof(cnt));
     if (p.mean_k < 1 || p.mean_k > kMaxMeanK || !(p.cluster_seed_radius >= 0.f) || !(p.denoise_radius >= 0.f) ||
         !std::isfinite(p.cluster_seed_radius) || !std::isfinite(p.denoise_radius))
-        return -1;
+        return kArg;
     if (n <= 0) return 0;
     int rc = denoise_reserve(b, n);
     if (rc) return rc;
@@ -699,7 +650,7 @@ int denoise_slam_map(DenoiseBuf& b, const float* d_pts, int64_t n, const Denoise
     slam_flag_kernel<<<nblk(n + 1), 256, 0, st>>>(d_pts, n, 2, 0.f, b.seed_id, b.flags);
     if ((rc = dn_scan_count(b, n, &cnt[4], st))) return rc;
     scatter_rows_kernel<<<nblk(n), 256, 0, st>>>(d_pts, n, 4, 4, b.flags, b.pos, d_out + 4 * (size_t)cnt[3]);
-    DCHK(hipGetLastError());
+    LIO_HIP(hipGetLastError());
     *n_out = cnt[3] + cnt[4];
     if (counts5) std::memcpy(counts5, cnt, sizeof(cnt));
     return 0;

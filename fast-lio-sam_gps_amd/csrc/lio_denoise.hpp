@@ -16,9 +16,9 @@ struct DnGeom {
     uint32_t ncells;
 };
 
-// Scratch of the denoise entry points: ONE device arena carved into the buffers below, sized for `cap`
-// points and grown geometrically (counted: lio_alloc_count), plus pinned host memory for the SOR distance
-// vector and the small counts.
+// Scratch of the denoise entry points: ONE device arena carved into the buffers below (denoise_reserve lists
+// them once, for lio_scratch.hpp's Carver), sized for `cap` points and grown geometrically (counted:
+// lio_alloc_count), plus pinned host memory for the SOR distance vector and the small counts.
 struct DenoiseBuf {
     void* arena = nullptr;
     size_t arena_bytes = 0;
@@ -57,7 +57,7 @@ void denoise_free(DenoiseBuf& b);
 int denoise_reserve(DenoiseBuf& b, int64_t n);
 
 // The building blocks the searches share (lio_cluster.hip uses them too), after denoise_reserve(b, >= n).  Status
-// as the entry points': 0, or -2 with the failed HIP call's text in last_error().
+// as the entry points' (lio_scratch.hpp): kOk, or kHip with the failed HIP call's text in last_error().
 // The grid of the finite points of d_pts in b.g4 (x, y, z, input index; cell order) / b.start (CSR offsets;
 // b.start[ncells] = finite points) / b.geom, enqueued (no host wait).  target > 0: cell edge from the density
 // (a 3x3x3 block holds about `target` points); target == 0: the edge is fixed_cell.  Either edge grows until

@@ -10,8 +10,8 @@ inline std::string& last_error() {
     return s;
 }
 // device / pinned allocations made by the library's growth paths (the loop leg's: ICP, grids, filters, scan
-// buffers) since the process started — lio_alloc_count(), which shows that a warm loop-closure sequence
-// allocates nothing
+// buffers; and the map updates') since the process started — lio_alloc_count(), which shows that a warm
+// loop-closure sequence allocates nothing
 inline std::atomic<int64_t>& alloc_counter() {
     static std::atomic<int64_t> n{0};
     return n;

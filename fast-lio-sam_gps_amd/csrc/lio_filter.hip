@@ -15,15 +15,13 @@
 // divides by the count (the PCL centroid; PCL sorts with std::sort, whose
 // order inside a voxel is unspecified — the stable order makes the float sums
 // reproducible).  Output in voxel-index order, as PCL.
-#include <hipcub/hipcub.hpp>
-
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
 
 #include "lio_dev.hpp"
-#include "lio_error.hpp"
+#include "lio_scratch_cub.hpp"
 #include "lio_filter.hpp"
 
 namespace lio {
@@ -592,91 +590,37 @@ __global__ void __launch_bounds__(256) undistort_gather_aabb_kernel(const float*
     if (threadIdx.x < 6) part[blockIdx.x * 6 + threadIdx.x] = s[threadIdx.x][0];
 }
 
-#define FCHK(x)                           \
-    do {                                  \
-        if ((x) != hipSuccess) return -2; \
-    } while (0)
-
-template <class T>
-int fgrow(T** p, int64_t& cap, int64_t need) {
-    if (need <= cap && *p) return 0;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    const int64_t c = std::max<int64_t>(need, cap + cap / 2);
-    count_alloc();
-    if (hipMalloc(p, (size_t)c * sizeof(T)) != hipSuccess) {
-        cap = 0;
-        return -5;
-    }
-    cap = c;
-    return 0;
-}
-
-int ftmp(FilterBuf& b, size_t need) {  // grown geometrically (1 MiB floor): no per-call re-allocation
-    if (need <= b.tmp_bytes && b.tmp) return 0;
-    if (b.tmp) (void)hipFree(b.tmp);
-    b.tmp = nullptr;
-    const size_t c = std::max(std::max(need, b.tmp_bytes + b.tmp_bytes / 2), (size_t)1 << 20);
-    count_alloc();
-    if (hipMalloc(&b.tmp, c) != hipSuccess) {
-        b.tmp_bytes = 0;
-        return -5;
-    }
-    b.tmp_bytes = c;
-    return 0;
-}
-
+// the per-point sort buffers for n points, the small fixed buffers on the first call, and the sort / scan
+// scratch for the whole capacity.  All or nothing: a failed growth leaves every per-point buffer null and cap 0.
 int reserve(FilterBuf& b, int64_t n) {
-    if (n <= b.cap && b.keys) return 0;
-    const int64_t c = std::max<int64_t>(std::max<int64_t>(n, b.cap + b.cap / 2), b.min_cap);
-    void* bufs[] = {b.keys, b.keys_alt, b.vals, b.vals_alt, b.head, b.vid};
-    for (void* p : bufs)
-        if (p) (void)hipFree(p);
-    count_alloc(6);
-    FCHK(hipMalloc(&b.keys, c * sizeof(uint32_t)));
-    FCHK(hipMalloc(&b.keys_alt, c * sizeof(uint32_t)));
-    FCHK(hipMalloc(&b.vals, c * sizeof(uint32_t)));
-    FCHK(hipMalloc(&b.vals_alt, c * sizeof(uint32_t)));
-    FCHK(hipMalloc(&b.head, (c + 1) * sizeof(uint32_t)));
-    FCHK(hipMalloc(&b.vid, (c + 1) * sizeof(uint32_t)));
+    if (n <= b.cap && b.keys) return kOk;
+    const int64_t c = grown(n, b.cap, b.min_cap);
+    b.cap = 0;
+    int rc = dev_alloc_all({dev_req(b.keys, c), dev_req(b.keys_alt, c), dev_req(b.vals, c), dev_req(b.vals_alt, c),
+                            dev_req(b.head, c + 1), dev_req(b.vid, c + 1)});
+    if (rc) return rc;
     b.cap = c;
-    if (!b.part) FCHK(hipMalloc(&b.part, 6 * kPartBlocks * sizeof(float)));
-    if (!b.geom) FCHK(hipMalloc(&b.geom, sizeof(VoxelGeom)));
+    if (!b.part) LIO_HIP(hipMalloc(&b.part, 6 * kPartBlocks * sizeof(float)));
+    if (!b.geom) LIO_HIP(hipMalloc(&b.geom, sizeof(VoxelGeom)));
     if (!b.h_small) {
-        FCHK(hipHostMalloc(&b.h_small, 256, hipHostMallocMapped));
-        FCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&b.d_small), b.h_small, 0));
+        LIO_HIP(hipHostMalloc(&b.h_small, 256, hipHostMallocMapped));
+        LIO_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&b.d_small), b.h_small, 0));
     }
     if (!b.cnt) {  // [0] selected count, [2] key-width flag (zero between launches)
-        FCHK(hipMalloc(&b.cnt, 64));
-        FCHK(hipMemset(b.cnt, 0, 64));
+        LIO_HIP(hipMalloc(&b.cnt, 64));
+        LIO_HIP(hipMemset(b.cnt, 0, 64));
     }
     // the sort / scan scratch for the whole capacity now, so a call up to it never re-allocates the scratch
     size_t sb = 0, xb = 0;
-    FCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, sb, b.keys, b.keys_alt, b.vals, b.vals_alt, (int)c, 0, 32));
-    FCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, xb, b.head, b.vid, (int)(c + 1)));
-    return ftmp(b, std::max(sb, xb));
-}
-
-int exscan(FilterBuf& b, const uint32_t* in, uint32_t* out, int64_t n1, hipStream_t st) {
-    size_t bytes = 0;
-    FCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, in, out, (int)n1, st));
-    if (ftmp(b, bytes)) return -5;
-    bytes = b.tmp_bytes;
-    FCHK(hipcub::DeviceScan::ExclusiveSum(b.tmp, bytes, in, out, (int)n1, st));
-    return 0;
+    LIO_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, sb, b.keys, b.keys_alt, b.vals, b.vals_alt, (int)c, 0, 32));
+    LIO_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, xb, b.head, b.vid, (int)(c + 1)));
+    return grow_scratch(&b.tmp, b.tmp_bytes, std::max(sb, xb));
 }
 
 // stable sort of (keys, vals) on key bits [0, bits) into (keys_alt, vals_alt)
 int sort_pairs(FilterBuf& b, int64_t n, hipStream_t st, int bits = 32) {
-    size_t bytes = 0;
-    FCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, b.keys, b.keys_alt, b.vals, b.vals_alt, (int)n, 0, bits, st));
-    if (ftmp(b, bytes)) return -5;
-    bytes = b.tmp_bytes;
-    FCHK(hipcub::DeviceRadixSort::SortPairs(b.tmp, bytes, b.keys, b.keys_alt, b.vals, b.vals_alt, (int)n, 0, bits, st));
-    return 0;
+    return cub_sort_pairs(b.tmp, b.tmp_bytes, kGrowScratch, b.keys, b.keys_alt, b.vals, b.vals_alt, n, bits, st);
 }
-
-inline int nblk(int64_t n) { return (int)std::max<int64_t>(1, (n + 255) / 256); }
 
 __global__ void records_xyz_kernel(const float* __restrict__ rec, int64_t n, int stride, float* __restrict__ xyz) {
     const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
@@ -751,24 +695,24 @@ __global__ void cloud_encode_kernel(const float* __restrict__ rec, int64_t n, in
 int cloud_decode(const uint8_t* d_data, int64_t n, int point_step, bool big_endian, const CloudField* fields, int nf,
                  float* d_out, hipStream_t st) {
     if (n <= 0) return 0;
-    if (nf < 1 || nf > kMaxFields || point_step <= 0) return -1;
+    if (nf < 1 || nf > kMaxFields || point_step <= 0) return kArg;
     CloudField f[kMaxFields] = {};
     for (int k = 0; k < nf; ++k) f[k] = fields[k];
     cloud_decode_kernel<<<nblk(n), 256, 0, st>>>(d_data, n, point_step, big_endian ? 1 : 0, f[0], f[1], f[2], f[3],
                                                  f[4], f[5], f[6], f[7], nf, d_out);
-    FCHK(hipGetLastError());
+    LIO_HIP(hipGetLastError());
     return 0;
 }
 
 int cloud_encode(const float* d_rec, int64_t n, int stride, int point_step, const CloudField* fields, int nf,
                  uint8_t* d_data, hipStream_t st) {
     if (n <= 0) return 0;
-    if (nf < 1 || nf > kMaxFields || point_step <= 0) return -1;
+    if (nf < 1 || nf > kMaxFields || point_step <= 0) return kArg;
     CloudField f[kMaxFields] = {};
     for (int k = 0; k < nf; ++k) f[k] = fields[k];
     cloud_encode_kernel<<<nblk(n), 256, 0, st>>>(d_rec, n, stride, point_step, f[0], f[1], f[2], f[3], f[4], f[5],
                                                  f[6], f[7], nf, d_data);
-    FCHK(hipGetLastError());
+    LIO_HIP(hipGetLastError());
     return 0;
 }
 
@@ -785,22 +729,20 @@ __global__ void records_xyz_sel_kernel(const float* __restrict__ rec, int64_t n,
 int records_to_xyz_sel(const float* d_rec, int64_t n, int stride, float* d_xyz, uint8_t* sel, hipStream_t st) {
     if (n <= 0) return 0;
     records_xyz_sel_kernel<<<nblk(n), 256, 0, st>>>(d_rec, n, stride, d_xyz, sel);
-    FCHK(hipGetLastError());
+    LIO_HIP(hipGetLastError());
     return 0;
 }
 
 int records_to_xyz(const float* d_rec, int64_t n, int stride, float* d_xyz, hipStream_t st) {
     if (n <= 0) return 0;
     records_xyz_kernel<<<nblk(n), 256, 0, st>>>(d_rec, n, stride, d_xyz);
-    FCHK(hipGetLastError());
+    LIO_HIP(hipGetLastError());
     return 0;
 }
 
 void filter_free(FilterBuf& b) {
-    void* bufs[] = {b.keys, b.keys_alt, b.vals, b.vals_alt, b.head, b.vid,
-                    b.part, b.geom,     b.tmp,  b.a,    b.c,        b.aux,  b.cnt};
-    for (void* p : bufs)
-        if (p) (void)hipFree(p);
+    dev_free(&b.keys, &b.keys_alt, &b.vals, &b.vals_alt, &b.head, &b.vid, &b.part, &b.geom, &b.tmp, &b.a, &b.c, &b.aux,
+             &b.cnt);
     if (b.h_small) (void)hipHostFree(b.h_small);
     if (b.h_stage) (void)hipHostFree(b.h_stage);
     b = FilterBuf{};
@@ -813,25 +755,26 @@ void filter_free(FilterBuf& b) {
 // nbp > 0: the producer of d_in already wrote nbp AABB partials into b.part (undistort_gather_aabb_kernel)
 int voxel_grid_enqueue(FilterBuf& b, const float* d_in, int64_t n, const uint32_t* cnt, int stride, const float leaf[3],
                        float* d_out, hipStream_t st, float* xyz = nullptr, uint8_t* sel = nullptr, int nbp = 0) {
-    if (stride < 3 || stride > kMaxFields || n >= (int64_t)0x7fffffff) return -1;
-    if (reserve(b, n)) return -5;
+    if (stride < 3 || stride > kMaxFields || n >= (int64_t)0x7fffffff) return kArg;
+    int rc = reserve(b, n);
+    if (rc) return rc;
     auto* hgeom = reinterpret_cast<VoxelGeom*>(b.d_small + 1);
     if (nbp <= 0) {  // no producer wrote the AABB partials: one pass over the input
-        if (cnt) return -1;  // (the scan path's rows in use come with the undistortion's partials)
+        if (cnt) return kArg;  // (the scan path's rows in use come with the undistortion's partials)
         nbp = (int)std::min<int64_t>(1024, (n + 255) / 256);
         minmax_partial_kernel<<<nbp, 256, 0, st>>>(d_in, n, stride, b.part);
     }
     const int bits = std::min(std::max(b.vox_bits, 1), 32);
     voxel_key_kernel<<<nblk(n), 256, 0, st>>>(d_in, n, cnt, stride, b.part, nbp, leaf[0], leaf[1], leaf[2], hgeom,
                                               b.keys, b.vals, bits, b.cnt + 2);
-    int rc = sort_pairs(b, n, st, bits);
+    rc = sort_pairs(b, n, st, bits);
     if (rc) return rc;
     // runs -> [start, end) per voxel (b.keys / b.vals are free after the sort); the count at b.vid[n]
     if (runs_one_block(n)) {
         voxel_runs_block_kernel<<<1, 1024, 0, st>>>(b.keys_alt, n, b.keys, b.vals, b.vid + n, b.cnt + 2, b.d_small);
     } else {
         run_head_kernel<<<nblk(n + 1), 256, 0, st>>>(b.keys_alt, n, b.head);
-        rc = exscan(b, b.head, b.vid, n + 1, st);
+        rc = cub_exclusive_sum(b.tmp, b.tmp_bytes, kGrowScratch, static_cast<const uint32_t*>(b.head), b.vid, n + 1, st);
         if (rc) return rc;
         voxel_bounds_kernel<<<nblk(n), 256, 0, st>>>(b.keys_alt, n, b.head, b.vid, b.keys, b.vals, b.cnt + 2,
                                                      b.d_small);
@@ -839,8 +782,14 @@ int voxel_grid_enqueue(FilterBuf& b, const float* d_in, int64_t n, const uint32_
     const int nbw = (int)std::min<int64_t>(kWaveCentroidBlocks, (n + 3) / 4);
     voxel_centroid_wave_kernel<<<std::max(nbw, 1), 256, 0, st>>>(d_in, stride, b.vals_alt, b.keys, b.vals, b.vid + n,
                                                                  d_out, xyz, sel);
-    FCHK(hipGetLastError());
+    LIO_HIP(hipGetLastError());
     return 0;
+}
+
+// two attempts and the key width still too narrow: the second runs at full width, so this is a device fault
+static int key_width_unsettled() {
+    last_error() = "voxel key width flag still set at 32 bits";
+    return kHip;
 }
 
 // After the stream has drained: the voxel count; 2 when the key width was too narrow (b.vox_bits reset to
@@ -860,7 +809,7 @@ static int voxel_grid_result(FilterBuf& b, const float* d_in, int64_t m, int str
     b.vox_bits = g.overflow ? 32 : std::min(32, g.key_bits + 1);
     if (g.overflow) {
         if (m > 0) copy_strided_kernel<<<nblk(m * stride), 256, 0, st>>>(d_in, m * stride, d_out);
-        FCHK(hipGetLastError());
+        LIO_HIP(hipGetLastError());
         *n_out = m;
         return 1;
     }
@@ -876,20 +825,21 @@ int voxel_grid(FilterBuf& b, const float* d_in, int64_t n, int stride, const flo
     for (int attempt = 0; attempt < 2 && rc == 2; ++attempt) {
         rc = voxel_grid_enqueue(b, d_in, n, nullptr, stride, leaf, d_out, st);
         if (rc) return rc;
-        FCHK(hipStreamSynchronize(st));
+        LIO_HIP(hipStreamSynchronize(st));
         rc = voxel_grid_result(b, d_in, n, stride, d_out, n_out, st);
     }
-    if (rc < 0 || rc == 2) return rc < 0 ? rc : -2;
-    if (rc == 1) FCHK(hipStreamSynchronize(st));
+    if (rc == 2) return key_width_unsettled();
+    if (rc < 0) return rc;
+    if (rc == 1) LIO_HIP(hipStreamSynchronize(st));
     return 0;
 }
 
 int transform_segments(const float* d_in, int64_t n, int stride, const int64_t* d_seg_off, int nseg,
                        const double* d_T16, float* d_out, hipStream_t st) {
     if (n <= 0) return 0;
-    if (stride < 3) return -1;
+    if (stride < 3) return kArg;
     transform_segs_kernel<<<nblk(n), 256, 0, st>>>(d_in, n, stride, d_seg_off, nseg, d_T16, d_out);
-    FCHK(hipGetLastError());
+    LIO_HIP(hipGetLastError());
     return 0;
 }
 
@@ -919,11 +869,11 @@ __global__ void keyframe_cloud_kernel(const float* __restrict__ rec, int64_t n, 
 int keyframe_cloud(const float* d_rec, int64_t n, int stride, const PoseArg& ps, const double* T16, float* d_out,
                    hipStream_t st) {
     if (n <= 0) return 0;
-    if (stride < 4) return -1;
+    if (stride < 4) return kArg;
     Mat16d T;
     for (int k = 0; k < 16; ++k) T.m[k] = T16[k];
     keyframe_cloud_kernel<<<nblk(n), 256, 0, st>>>(d_rec, n, stride, ps, T, d_out);
-    FCHK(hipGetLastError());
+    LIO_HIP(hipGetLastError());
     return 0;
 }
 
@@ -934,9 +884,10 @@ int scan_preprocess_enqueue(FilterBuf& b, const float* d_raw, int64_t n, int str
     b.prep_sel = -1;
     if (n <= 0) return 0;
     if (stride < 4 || stride > kMaxFields || p.time_field < 3 || p.time_field >= stride || n >= (int64_t)0x7fffffff)
-        return -1;
-    if (reserve(b, n)) return -5;
-    int rc = fgrow(&b.c, b.c_cap, n * stride);
+        return kArg;
+    int rc = reserve(b, n);
+    if (rc) return rc;
+    rc = grow_buf(&b.c, b.c_cap, n * stride);
     if (rc) return rc;
     const uint32_t* cnt = nullptr;  // rows in use past this point: all n (host selection) or b.cnt[0]
     // the undistortion writes the AABB partials of its rows when the voxel grid follows (one pass fewer)
@@ -979,14 +930,14 @@ int scan_preprocess_enqueue(FilterBuf& b, const float* d_raw, int64_t n, int str
         }
         return voxel_grid_enqueue(b, b.c, n, cnt, stride, leaf, d_out, st, xyz, sel, fuse ? nblk(n) : 0);
     }
-    FCHK(hipMemcpyAsync(d_out, b.c, (size_t)n * stride * sizeof(float), hipMemcpyDeviceToDevice, st));
+    LIO_HIP(hipMemcpyAsync(d_out, b.c, (size_t)n * stride * sizeof(float), hipMemcpyDeviceToDevice, st));
     return 0;
 }
 
 int scan_preprocess_finish(FilterBuf& b, int stride, float* d_out, int64_t* n_out, int64_t* n_undist, hipStream_t st) {
     *n_out = 0;
     if (n_undist) *n_undist = 0;
-    FCHK(hipStreamSynchronize(st));
+    LIO_HIP(hipStreamSynchronize(st));
     if (b.prep_n <= 0) return 0;
     const int64_t m = b.prep_sel >= 0 ? b.prep_sel : (uint32_t)b.h_small[kHostSel];
     if (n_undist) *n_undist = m;
@@ -1008,8 +959,9 @@ int scan_preprocess(FilterBuf& b, const float* d_raw, int64_t n, int stride, con
         if (rc) return rc;
         rc = scan_preprocess_finish(b, stride, d_out, n_out, n_undist, st);
     }
-    if (rc < 0 || rc == 2) return rc < 0 ? rc : -2;
-    if (rc == 1) FCHK(hipStreamSynchronize(st));
+    if (rc == 2) return key_width_unsettled();
+    if (rc < 0) return rc;
+    if (rc == 1) LIO_HIP(hipStreamSynchronize(st));
     return 0;
 }
 

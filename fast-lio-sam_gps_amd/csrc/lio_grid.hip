@@ -4,14 +4,11 @@
 // Layout rationale: the kNN reads a query's neighbour cells as short runs of
 // contiguous 16-B points; x is the fastest grid axis so a 3-cell row is one
 // contiguous run of the sorted array and one or two cache lines of start[].
-#include <hipcub/hipcub.hpp>
-
 #include <algorithm>
 #include <cmath>
-#include <cstdio>
 #include <cstring>
 
-#include "lio_error.hpp"
+#include "lio_scratch_cub.hpp"
 #include "lio_grid_dev.hpp"
 #include "lio_kernels.hpp"
 
@@ -254,35 +251,9 @@ __global__ void insert_clear_kernel(uint32_t* __restrict__ addc, const uint32_t*
     if (k < *d_ntouch) addc[tlist[k]] = 0u;
 }
 
-#define HIPCHK(x)                                                               \
-    do {                                                                        \
-        hipError_t e_ = (x);                                                    \
-        if (e_ != hipSuccess) {                                                 \
-            fprintf(stderr, "lio_grid: %s -> %s\n", #x, hipGetErrorString(e_)); \
-            return -2;                                                          \
-        }                                                                       \
-    } while (0)
-
-// scratch grown geometrically (1 MiB floor): no re-allocation (a device-wide sync) per slightly larger call
-static int ensure(void** p, size_t& cap_bytes, size_t need) {
-    if (need <= cap_bytes && *p) return 0;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    const size_t c = std::max(std::max(need, cap_bytes + cap_bytes / 2), (size_t)1 << 20);
-    count_alloc();
-    if (hipMalloc(p, c) != hipSuccess) {
-        cap_bytes = 0;
-        return -5;
-    }
-    cap_bytes = c;
-    return 0;
-}
-
 void grid_free(GridBuf& g) {
-    void* ptrs[] = {g.pts, g.by_id, g.start, g.keys, g.keys_alt, g.vals, g.vals_alt, g.tmp, g.aabb, g.xyz,
-                    g.ckeys, g.rng, g.lim, g.addc, g.dirty, g.bump};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
+    dev_free(&g.pts, &g.by_id, &g.start, &g.keys, &g.keys_alt, &g.vals, &g.vals_alt, &g.tmp, &g.aabb, &g.xyz, &g.ckeys,
+             &g.rng, &g.lim, &g.addc, &g.dirty, &g.bump);
     if (g.aabb_host) (void)hipHostFree(g.aabb_host);
     const bool gapped = g.gapped;
     g = GridBuf{};
@@ -309,14 +280,13 @@ GridDev grid_view(const GridBuf& g) {
 
 int grid_reserve_ids(GridBuf& g, int64_t n_ids, hipStream_t st) {
     if (n_ids <= g.id_cap && g.by_id) return 0;
-    const int64_t cap = std::max<int64_t>(std::max<int64_t>(n_ids, g.id_cap + g.id_cap / 2), g.min_entries);
-    float4* nb = nullptr;
-    count_alloc();
-    HIPCHK(hipMalloc(&nb, cap * sizeof(float4)));
+    const int64_t cap = grown(n_ids, g.id_cap, g.min_entries);
+    float4* nb = nullptr;  // the ids are kept: the new buffer beside the old one until they are copied
+    if (dev_alloc_all({dev_req(nb, cap)})) return kNoMem;
     if (g.by_id) {
-        if (g.n_ids) HIPCHK(hipMemcpyAsync(nb, g.by_id, g.n_ids * sizeof(float4), hipMemcpyDeviceToDevice, st));
-        HIPCHK(hipStreamSynchronize(st));
-        HIPCHK(hipFree(g.by_id));
+        if (g.n_ids) LIO_HIP(hipMemcpyAsync(nb, g.by_id, g.n_ids * sizeof(float4), hipMemcpyDeviceToDevice, st));
+        LIO_HIP(hipStreamSynchronize(st));
+        LIO_HIP(hipFree(g.by_id));
     }
     g.by_id = nb;
     g.id_cap = cap;
@@ -326,67 +296,50 @@ int grid_reserve_ids(GridBuf& g, int64_t n_ids, hipStream_t st) {
 // per-entry buffers for n ids: the (key, id) sort scratch, and for dense grids the cell-sorted
 // arrays (gapped grids keep their points in the slot pool, reserve_slots)
 static int reserve_entries(GridBuf& g, int64_t n) {
-    if (n <= g.cap && g.keys) return 0;
-    const int64_t cap = std::max<int64_t>(std::max<int64_t>(n, g.cap + g.cap / 2), g.min_entries);
-    count_alloc(g.gapped ? 4 : 6);
-    void* bufs[] = {g.keys, g.keys_alt, g.vals, g.vals_alt};
-    for (void* p : bufs)
-        if (p) HIPCHK(hipFree(p));
-    HIPCHK(hipMalloc(&g.keys, cap * sizeof(uint32_t)));
-    HIPCHK(hipMalloc(&g.keys_alt, cap * sizeof(uint32_t)));
-    HIPCHK(hipMalloc(&g.vals, cap * sizeof(uint32_t)));
-    HIPCHK(hipMalloc(&g.vals_alt, cap * sizeof(uint32_t)));
-    if (!g.gapped) {
-        if (g.pts) HIPCHK(hipFree(g.pts));
-        if (g.ckeys) HIPCHK(hipFree(g.ckeys));
-        g.pts = nullptr;
-        g.ckeys = nullptr;
-        HIPCHK(hipMalloc(&g.pts, cap * sizeof(float4)));
-        HIPCHK(hipMalloc(&g.ckeys, cap * sizeof(uint32_t)));
+    if (n <= g.cap && g.keys) return kOk;
+    const int64_t cap = grown(n, g.cap, g.min_entries);
+    g.cap = 0;
+    int rc = dev_alloc_all({dev_req(g.keys, cap), dev_req(g.keys_alt, cap), dev_req(g.vals, cap), dev_req(g.vals_alt, cap)});
+    if (!rc && !g.gapped) rc = dev_alloc_all({dev_req(g.pts, cap), dev_req(g.ckeys, cap)});
+    if (rc) {
+        dev_free(&g.keys, &g.keys_alt, &g.vals, &g.vals_alt);
+        return rc;
     }
     g.cap = cap;
-    return 0;
+    return kOk;
 }
 
 // gapped grids: the slot pool (contents are rewritten by the rebuild that asks for it)
 static int reserve_slots(GridBuf& g, int64_t slots) {
-    if (slots <= g.slots_cap && g.pts) return 0;
-    if (slots >= (int64_t)0xffffffffu) return -1;
-    if (g.pts) HIPCHK(hipFree(g.pts));
-    g.pts = nullptr;
+    if (slots <= g.slots_cap && g.pts) return kOk;
+    if (slots >= (int64_t)0xffffffffu) return kArg;
     g.slots_cap = 0;
-    count_alloc();
-    HIPCHK(hipMalloc(&g.pts, (size_t)slots * sizeof(float4)));
+    if (dev_alloc_all({dev_req(g.pts, (size_t)slots)})) return kNoMem;
     g.slots_cap = slots;
-    return 0;
+    return kOk;
 }
 
 static int reserve_cells(GridBuf& g, uint32_t nc1) {
-    if (nc1 <= g.cells_cap && g.start) return 0;
-    void* bufs[] = {g.start, g.rng, g.lim, g.addc, g.dirty};
-    for (void* p : bufs)
-        if (p) HIPCHK(hipFree(p));
-    g.start = nullptr;
-    g.rng = nullptr;
-    g.lim = nullptr;
-    g.addc = nullptr;
-    g.dirty = nullptr;
-    const uint32_t cap = std::max<uint32_t>(std::max<uint32_t>(nc1, g.cells_cap + g.cells_cap / 2), g.min_cells);
-    count_alloc(g.gapped ? 5 : 1);
-    HIPCHK(hipMalloc(&g.start, 2 * (size_t)cap * sizeof(uint32_t)));  // + histogram scratch
-    if (g.gapped) {
-        HIPCHK(hipMalloc(&g.rng, (size_t)cap * sizeof(uint2)));
-        HIPCHK(hipMalloc(&g.lim, (size_t)cap * sizeof(uint32_t)));
-        HIPCHK(hipMalloc(&g.addc, (size_t)cap * sizeof(uint32_t)));
-        HIPCHK(hipMalloc(&g.dirty, (size_t)cap + 4));  // + 4: flagged through 32-bit words
-        if (!g.bump) HIPCHK(hipMalloc(&g.bump, sizeof(uint32_t)));
+    if (nc1 <= g.cells_cap && g.start) return kOk;
+    const size_t cap = grown<uint32_t>(nc1, g.cells_cap, g.min_cells);
+    g.cells_cap = 0;
+    dev_free(&g.start, &g.rng, &g.lim, &g.addc, &g.dirty);
+    int rc = dev_alloc_all({dev_req(g.start, 2 * cap)});  // + histogram scratch
+    if (!rc && g.gapped) {
+        rc = dev_alloc_all({dev_req(g.rng, cap), dev_req(g.lim, cap), dev_req(g.addc, cap),
+                            dev_req(g.dirty, cap + 4)});  // + 4: flagged through 32-bit words
+        if (!rc && !g.bump) LIO_HIP(hipMalloc(&g.bump, sizeof(uint32_t)));
     }
-    g.cells_cap = cap;
-    return 0;
+    if (rc) {
+        dev_free(&g.start);
+        return rc;
+    }
+    g.cells_cap = (uint32_t)cap;
+    return kOk;
 }
 
 int grid_build(GridBuf& g, const float* d_xyz, int64_t n, float cell, hipStream_t st) {
-    if (n <= 0 || n >= (int64_t)0x7fffffff) return -1;
+    if (n <= 0 || n >= (int64_t)0x7fffffff) return kArg;
     g.n_ids = 0;
     // 1.5x headroom: the first map_incremental calls append without re-allocating (and copying) the map
     const int64_t room = n + n / 2;
@@ -405,15 +358,15 @@ int grid_rebuild(GridBuf& g, float cell, float slack, hipStream_t st) {
     if (!(cell > 0.f)) cell = 1.0f;
     int rc = reserve_entries(g, std::max<int64_t>(n_ids, 1));
     if (rc) return rc;
-    if (!g.aabb) HIPCHK(hipMalloc(&g.aabb, 8 * 1024 * sizeof(float) + 64));  // result + 8-word partials
-    if (!g.aabb_host) HIPCHK(hipHostMalloc(&g.aabb_host, 64));
+    if (!g.aabb) LIO_HIP(hipMalloc(&g.aabb, 8 * 1024 * sizeof(float) + 64));  // result + 8-word partials
+    if (!g.aabb_host) LIO_HIP(hipHostMalloc(&g.aabb_host, 64));
     // ---- AABB + alive count
     const int nbA = (int)std::max<int64_t>(1, std::min<int64_t>(1024, (n_ids + 255) / 256));
     float* part = g.aabb + 8;
     if (n_ids) aabb_partial_kernel<<<nbA, 256, 0, st>>>(g.by_id, n_ids, part);
     aabb_final_kernel<<<1, 256, 0, st>>>(part, n_ids ? nbA : 0, g.aabb);
-    HIPCHK(hipMemcpyAsync(g.aabb_host, g.aabb, 7 * sizeof(float), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    LIO_HIP(hipMemcpyAsync(g.aabb_host, g.aabb, 7 * sizeof(float), hipMemcpyDeviceToHost, st));
+    LIO_HIP(hipStreamSynchronize(st));
     const float* bb = g.aabb_host;
     uint32_t n_alive = 0;
     std::memcpy(&n_alive, bb + 6, sizeof(uint32_t));
@@ -422,7 +375,7 @@ int grid_rebuild(GridBuf& g, float cell, float slack, hipStream_t st) {
         geo = GridGeom{0.f, 0.f, 0.f, cell, 1, 1, 1, 1u};
     } else {
         for (int d = 0; d < 6; ++d)
-            if (!std::isfinite(bb[d])) return -1;
+            if (!std::isfinite(bb[d])) return kArg;
         // geometry: slack + 1-cell pad on every side; grow the cell if the table would exceed 2^29 cells
         for (;;) {
             double o[3], ext[3];
@@ -451,31 +404,29 @@ int grid_rebuild(GridBuf& g, float cell, float slack, hipStream_t st) {
     rc = reserve_cells(g, nc1);
     if (rc) return rc;
     uint32_t* counts = g.start + g.cells_cap;
-    HIPCHK(hipMemsetAsync(counts, 0, (size_t)nc1 * sizeof(uint32_t), st));
+    LIO_HIP(hipMemsetAsync(counts, 0, (size_t)nc1 * sizeof(uint32_t), st));
     const int nb = (int)std::max<int64_t>(1, (n_ids + 255) / 256);
     if (n_ids) cell_key_kernel<<<nb, 256, 0, st>>>(g.by_id, n_ids, geo, g.keys, g.vals);
     // ---- sort (key, id): stable, so ids ascend inside a cell; dead ids (key ncells) last
     int bits = 1;
     while (bits < 32 && ((uint64_t)1 << bits) <= (uint64_t)geo.ncells) ++bits;
+    // the scratch for the largest of the sort and the scans now: nothing below re-allocates it
     size_t sort_bytes = 0, scan_bytes = 0;
-    HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, g.keys, g.keys_alt, g.vals, g.vals_alt,
-                                              (int)std::max<int64_t>(n_ids, 1), 0, bits, st));
-    HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, counts, g.start, (int)nc1, st));
-    size_t need = std::max(sort_bytes, scan_bytes);
-    if (ensure(&g.tmp, g.tmp_bytes, need) != 0) return -5;
-    size_t tb = g.tmp_bytes;
+    LIO_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, g.keys, g.keys_alt, g.vals, g.vals_alt,
+                                               (int)std::max<int64_t>(n_ids, 1), 0, bits, st));
+    LIO_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, counts, g.start, (int)nc1, st));
+    if ((rc = grow_scratch(&g.tmp, g.tmp_bytes, std::max(sort_bytes, scan_bytes)))) return rc;
     if (n_ids) {
-        HIPCHK(hipcub::DeviceRadixSort::SortPairs(g.tmp, tb, g.keys, g.keys_alt, g.vals, g.vals_alt, (int)n_ids, 0,
-                                                  bits, st));
+        rc = cub_sort_pairs(g.tmp, g.tmp_bytes, kGrowScratch, g.keys, g.keys_alt, g.vals, g.vals_alt, n_ids, bits, st);
+        if (rc) return rc;
         sorted_counts_kernel<<<nb, 256, 0, st>>>(g.keys_alt, n_ids, geo.ncells, counts);
     }
-    tb = g.tmp_bytes;
-    HIPCHK(hipcub::DeviceScan::ExclusiveSum(g.tmp, tb, counts, g.start, (int)nc1, st));
+    if ((rc = cub_exclusive_sum(g.tmp, g.tmp_bytes, kGrowScratch, counts, g.start, nc1, st))) return rc;
     if (!g.gapped) {
         if (n_alive)
             gather_kernel<<<(int)((n_alive + 255) / 256), 256, 0, st>>>(g.by_id, n_alive, g.vals_alt, g.keys_alt,
                                                                         g.pts, g.ckeys);
-        HIPCHK(hipGetLastError());
+        LIO_HIP(hipGetLastError());
         g.n = n_alive;
         return 0;
     }
@@ -483,14 +434,13 @@ int grid_rebuild(GridBuf& g, float cell, float slack, hipStream_t st) {
     uint32_t* gbase = counts;
     const int nbc = (int)((nc1 + 255) / 256);
     cap_kernel<<<nbc, 256, 0, st>>>(g.start, geo.ncells, g.lim);
-    tb = g.tmp_bytes;
-    HIPCHK(hipcub::DeviceScan::ExclusiveSum(g.tmp, tb, g.lim, gbase, (int)nc1, st));
+    if ((rc = cub_exclusive_sum(g.tmp, g.tmp_bytes, kGrowScratch, g.lim, gbase, nc1, st))) return rc;
     rng_kernel<<<nbc, 256, 0, st>>>(g.start, gbase, geo.ncells, g.rng, g.lim, g.bump);
-    HIPCHK(hipMemsetAsync(g.addc, 0, (size_t)geo.ncells * sizeof(uint32_t), st));
-    HIPCHK(hipMemsetAsync(g.dirty, 0, (size_t)geo.ncells, st));
+    LIO_HIP(hipMemsetAsync(g.addc, 0, (size_t)geo.ncells * sizeof(uint32_t), st));
+    LIO_HIP(hipMemsetAsync(g.dirty, 0, (size_t)geo.ncells, st));
     uint32_t used = 0;
-    HIPCHK(hipMemcpyAsync(g.aabb_host + 9, gbase + geo.ncells, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    LIO_HIP(hipMemcpyAsync(g.aabb_host + 9, gbase + geo.ncells, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    LIO_HIP(hipStreamSynchronize(st));
     std::memcpy(&used, g.aabb_host + 9, sizeof(uint32_t));
     // pool: the blocks + room for the cells that will outgrow theirs before the next rebuild
     const int64_t pool = (int64_t)used + std::max<int64_t>((int64_t)1 << 20, (int64_t)used / 2);
@@ -499,7 +449,7 @@ int grid_rebuild(GridBuf& g, float cell, float slack, hipStream_t st) {
     if (n_alive)
         gather_gapped_kernel<<<(int)((n_alive + 255) / 256), 256, 0, st>>>(g.by_id, n_alive, g.vals_alt, g.keys_alt,
                                                                            g.start, g.rng, g.pts);
-    HIPCHK(hipGetLastError());
+    LIO_HIP(hipGetLastError());
     g.slots_used = used;
     g.n = n_alive;
     return 0;

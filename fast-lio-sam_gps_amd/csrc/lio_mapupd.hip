@@ -16,7 +16,6 @@
 // enqueued with ONE host synchronisation at its end (the counts stay on the
 // device; launch sizes are the call's upper bounds).
 // Semantics restated in oracle/lio_oracle.cpp (DynMap, map_incremental).
-#include <hipcub/hipcub.hpp>
 #include <rocprim/block/block_radix_sort.hpp>
 #include <rocprim/block/block_scan.hpp>
 
@@ -27,6 +26,7 @@
 #include "lio_grid_dev.hpp"
 #include "lio_kernels.hpp"
 #include "lio_mapupd.hpp"
+#include "lio_scratch_cub.hpp"
 
 namespace lio {
 
@@ -1068,112 +1068,45 @@ __global__ void incr_scatter_kernel(const float* __restrict__ world, const uint8
     o[2] = world[3 * i + 2];
 }
 
-#define UPD_CHK(x)                            \
-    do {                                      \
-        if ((x) != hipSuccess) return -2;     \
-    } while (0)
-
-template <class T>
-int ensure_buf(T** p, int64_t& cap, int64_t need) {
-    if (need <= cap && *p) return 0;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    const int64_t c = std::max<int64_t>(need, cap + cap / 2);
-    if (hipMalloc(p, (size_t)c * sizeof(T)) != hipSuccess) {
-        cap = 0;
-        return -5;
-    }
-    cap = c;
-    return 0;
-}
-
-// scan scratch: grown geometrically (1 MiB floor), so scans of varying size do not re-allocate
-// (hipFree synchronises the device) on every call that needs a little more
-int ensure_tmp(MapUpdBuf& u, size_t need) {
-    if (need <= u.tmp_bytes && u.tmp) return 0;
-    if (u.tmp) (void)hipFree(u.tmp);
-    u.tmp = nullptr;
-    const size_t c = std::max(std::max(need, u.tmp_bytes + u.tmp_bytes / 2), (size_t)1 << 20);
-    if (hipMalloc(&u.tmp, c) != hipSuccess) {
-        u.tmp_bytes = 0;
-        return -5;
-    }
-    u.tmp_bytes = c;
-    return 0;
-}
-
 // per-point scratch for calls of up to n points (the voxel table at <= 1/4 load).  The table is
 // initialised on `st`, the map's (non-blocking) stream: a plain hipMemset runs on the null stream,
 // which a non-blocking stream does not wait for.
 int ensure_pts(MapUpdBuf& u, int64_t n, hipStream_t st) {
     if (!u.cnt) {
-        UPD_CHK(hipMalloc(&u.cnt, kCntWords * sizeof(uint32_t)));
-        UPD_CHK(hipMemsetAsync(u.cnt, 0, kCntWords * sizeof(uint32_t), st));  // spread lines: cleared by their reader
-        UPD_CHK(hipHostMalloc(&u.h_cnt, 32 * sizeof(uint32_t)));
+        LIO_HIP(hipMalloc(&u.cnt, kCntWords * sizeof(uint32_t)));
+        LIO_HIP(hipMemsetAsync(u.cnt, 0, kCntWords * sizeof(uint32_t), st));  // spread lines: cleared by their reader
+        LIO_HIP(hipHostMalloc(&u.h_cnt, 32 * sizeof(uint32_t)));
     }
     if (n <= u.cap && u.world) return 0;
-    const int64_t c = std::max<int64_t>(n, u.cap + u.cap / 2);
-    void* bufs[] = {u.f64,   u.pos64, u.add_flag, u.pos,      u.cls,      u.world,    u.xyz_a, u.xyz_b, u.pending,
-                    u.skey,  u.sval,  u.skey2,    u.sval2,    u.xs,       u.vlist,    u.dlist,    u.tmp_cell, u.tmp_rank,
-                    u.tlist, u.hkey,  u.hhead,    u.hend,     u.vnruns,   u.runs, u.blk};
-    for (void* p : bufs)
-        if (p) (void)hipFree(p);
-    UPD_CHK(hipMalloc(&u.f64, (c + 1) * sizeof(unsigned long long)));
-    UPD_CHK(hipMalloc(&u.pos64, (c + 1) * sizeof(unsigned long long)));
-    UPD_CHK(hipMalloc(&u.add_flag, (c + 1) * sizeof(uint32_t)));
-    UPD_CHK(hipMalloc(&u.pos, (c + 1) * sizeof(uint32_t)));
-    UPD_CHK(hipMalloc(&u.cls, c + 64));
-    UPD_CHK(hipMalloc(&u.world, c * 3 * sizeof(float)));
-    UPD_CHK(hipMalloc(&u.xyz_a, c * 3 * sizeof(float)));
-    UPD_CHK(hipMalloc(&u.xyz_b, c * 3 * sizeof(float)));
-    UPD_CHK(hipMalloc(&u.pending, c * sizeof(int)));
-    UPD_CHK(hipMalloc(&u.skey, c * sizeof(uint32_t)));
-    UPD_CHK(hipMalloc(&u.sval, c * sizeof(uint32_t)));
-    UPD_CHK(hipMalloc(&u.skey2, c * sizeof(uint32_t)));
-    UPD_CHK(hipMalloc(&u.sval2, c * sizeof(uint32_t)));
-    UPD_CHK(hipMalloc(&u.xs, c * sizeof(float4)));
-    UPD_CHK(hipMalloc(&u.vlist, c * sizeof(uint32_t)));
-    UPD_CHK(hipMalloc(&u.dlist, c * 27 * sizeof(uint32_t)));  // dirty cells: <= 27 per voxel box at any cell size
-    UPD_CHK(hipMalloc(&u.tmp_cell, c * sizeof(uint32_t)));
-    UPD_CHK(hipMalloc(&u.tmp_rank, c * sizeof(uint32_t)));
-    UPD_CHK(hipMalloc(&u.tlist, c * sizeof(uint32_t)));
+    const size_t c = (size_t)grown<int64_t>(n, u.cap);
     uint32_t hc = 1024;
     int hb = 10;
-    while ((int64_t)hc < 4 * c) {
+    while ((int64_t)hc < 4 * (int64_t)c) {
         hc <<= 1;
         ++hb;
     }
-    UPD_CHK(hipMalloc(&u.hkey, (size_t)hc * sizeof(unsigned long long)));
-    UPD_CHK(hipMalloc(&u.hhead, (size_t)hc * sizeof(int)));
-    UPD_CHK(hipMalloc(&u.hend, (size_t)hc * sizeof(int)));
-    UPD_CHK(hipMalloc(&u.vnruns, (size_t)hc * sizeof(uint32_t)));
-    UPD_CHK(hipMalloc(&u.runs, c * sizeof(uint4)));  // a run holds >= 1 point
-    u.blk_cap = (c + kGrpB - 1) / kGrpB + 1;
-    UPD_CHK(hipMalloc(&u.blk, 2 * u.blk_cap * sizeof(uint32_t)));  // survivors | no-need per sort block
-    UPD_CHK(hipMemsetAsync(u.vnruns, 0, (size_t)hc * sizeof(uint32_t), st));
+    const size_t blk_cap = (c + kGrpB - 1) / kGrpB + 1;
+    u.cap = 0;
+    // every per-point buffer, once: all allocated, or (kNoMem) all null with cap 0
+    const int rc = dev_alloc_all({
+        dev_req(u.f64, c + 1), dev_req(u.pos64, c + 1), dev_req(u.add_flag, c + 1), dev_req(u.pos, c + 1),
+        dev_req(u.cls, c + 64), dev_req(u.world, c * 3), dev_req(u.xyz_a, c * 3), dev_req(u.xyz_b, c * 3),
+        dev_req(u.pending, c), dev_req(u.skey, c), dev_req(u.sval, c), dev_req(u.skey2, c), dev_req(u.sval2, c),
+        dev_req(u.xs, c), dev_req(u.vlist, c),
+        dev_req(u.dlist, c * 27),  // dirty cells: <= 27 per voxel box at any cell size
+        dev_req(u.tmp_cell, c), dev_req(u.tmp_rank, c), dev_req(u.tlist, c), dev_req(u.hkey, hc), dev_req(u.hhead, hc),
+        dev_req(u.hend, hc), dev_req(u.vnruns, hc),
+        dev_req(u.runs, c),               // a run holds >= 1 point
+        dev_req(u.blk, 2 * blk_cap),      // survivors | no-need per sort block
+    });
+    if (rc) return rc;
+    u.blk_cap = blk_cap;
+    LIO_HIP(hipMemsetAsync(u.vnruns, 0, (size_t)hc * sizeof(uint32_t), st));
     u.hbits = hb;
-    UPD_CHK(hipMemsetAsync(u.hkey, 0xff, (size_t)hc * sizeof(unsigned long long), st));  // empty keys
-    UPD_CHK(hipMemsetAsync(u.hhead, 0xff, (size_t)hc * sizeof(int), st));                // empty chains (-1)
+    LIO_HIP(hipMemsetAsync(u.hkey, 0xff, (size_t)hc * sizeof(unsigned long long), st));  // empty keys
+    LIO_HIP(hipMemsetAsync(u.hhead, 0xff, (size_t)hc * sizeof(int), st));                // empty chains (-1)
     u.hcap = hc;
     u.cap = c;
-    return 0;
-}
-
-int exclusive_scan(MapUpdBuf& u, const uint32_t* in, uint32_t* out, int n1, hipStream_t st) {
-    size_t bytes = 0;
-    UPD_CHK(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, in, out, n1, st));
-    if (ensure_tmp(u, bytes)) return -5;
-    bytes = u.tmp_bytes;
-    UPD_CHK(hipcub::DeviceScan::ExclusiveSum(u.tmp, bytes, in, out, n1, st));
-    return 0;
-}
-
-int exclusive_scan64(MapUpdBuf& u, const unsigned long long* in, unsigned long long* out, int n1, hipStream_t st) {
-    size_t bytes = 0;
-    UPD_CHK(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, in, out, n1, st));
-    if (ensure_tmp(u, bytes)) return -5;
-    bytes = u.tmp_bytes;
-    UPD_CHK(hipcub::DeviceScan::ExclusiveSum(u.tmp, bytes, in, out, n1, st));
     return 0;
 }
 
@@ -1190,26 +1123,20 @@ int enqueue_add(GridBuf& g, MapUpdBuf& u, const float* xyz, int n_max, const flo
                 hipStream_t st) {
     const int nb = (n_max + 255) / 256;
     vox_group_kernel<<<nb, 256, 0, st>>>(xyz, ds, u.hkey, u.hcap - 1, n_max, u.skey, u.sval, u.vlist, u.cnt);
-    {  // (slot, index) stable by slot: every voxel's points contiguous in input order (slot hcap: unused)
-        size_t bytes = 0;
-        UPD_CHK(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, u.skey, u.skey2, u.sval, u.sval2, n_max, 0,
-                                                   u.hbits + 1, st));
-        if (ensure_tmp(u, bytes)) return -5;
-        bytes = u.tmp_bytes;
-        UPD_CHK(hipcub::DeviceRadixSort::SortPairs(u.tmp, bytes, u.skey, u.skey2, u.sval, u.sval2, n_max, 0,
-                                                   u.hbits + 1, st));
-    }
+    // (slot, index) stable by slot: every voxel's points contiguous in input order (slot hcap: unused)
+    int rc = cub_sort_pairs(u.tmp, u.tmp_bytes, kGrowScratch, u.skey, u.skey2, u.sval, u.sval2, n_max, u.hbits + 1, st);
+    if (rc) return rc;
     vox_runs_kernel<<<nb, 256, 0, st>>>(u.skey2, u.sval2, xyz, n_max, u.hcap - 1, u.hhead, u.hend, u.xs);
     VoxArgs va{u.vlist, u.hkey, u.hhead, u.hend, nullptr, nullptr, u.sval2, u.xs, xyz, ds, grid_view(g), (int)g.n,
                g.pts, g.by_id, g.dirty, u.dlist, dcap_of(u), u.cnt, u.add_flag};
     vox_resolve_kernel<false><<<std::min(2048, (n_max + 3) / 4), 256, 0, st>>>(va);
-    int rc = exclusive_scan(u, u.add_flag, u.pos, n_max + 1, st);
+    rc = cub_exclusive_sum(u.tmp, u.tmp_bytes, kGrowScratch, static_cast<const uint32_t*>(u.add_flag), u.pos, n_max + 1, st);
     if (rc) return rc;
     append_kernel<<<nb, 256, 0, st>>>(xyz, u.add_flag, u.pos, xyz_nn, n_max, id0, g.by_id, u.cnt);
     grid_compact_cells(g, u.dlist, u.cnt + kCDirty, dcap_of(u), n_max * 27, st);
     GridInsertScratch sc{u.tmp_cell, u.tmp_rank, u.tlist, u.cnt + kCTouch};
     grid_insert_ids(g, id0, u.cnt + kCNew, n_max, sc, u.cnt + kCFlags, st);
-    UPD_CHK(hipGetLastError());
+    LIO_HIP(hipGetLastError());
     return 0;
 }
 
@@ -1232,7 +1159,7 @@ int enqueue_grouped(GridBuf& g, MapUpdBuf& u, const float* xyz, const uint8_t* c
     update_kernel<<<nblk + nb_comp, kGrpT, 0, st>>>(ua);
     GridInsertScratch sc{u.tmp_cell, u.tmp_rank, u.tlist, u.cnt + kCTouch};
     grid_insert_finish(g, id0, u.cnt + kCNew, n, sc, u.cnt + kCFlags, st);
-    UPD_CHK(hipGetLastError());
+    LIO_HIP(hipGetLastError());
     return 0;
 }
 
@@ -1241,8 +1168,8 @@ constexpr int kRedo = 1;  // finish_add: the grouped update was abandoned (kFlag
 // the one host synchronisation of an update: counts back, the map's host view updated; a point
 // outside the grid or an exhausted slot pool -> full rebuild (by_id is complete either way)
 int finish_add(GridBuf& g, MapUpdBuf& u, int64_t id0, float slack, hipStream_t st) {
-    UPD_CHK(hipMemcpyAsync(u.h_cnt, u.cnt, 16 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    UPD_CHK(hipStreamSynchronize(st));
+    LIO_HIP(hipMemcpyAsync(u.h_cnt, u.cnt, 16 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    LIO_HIP(hipStreamSynchronize(st));
     const uint32_t* c = u.h_cnt;
     if (c[kCFlags] & kFlagRuns) return kRedo;
     g.n_ids = id0 + c[kCNew];
@@ -1254,11 +1181,9 @@ int finish_add(GridBuf& g, MapUpdBuf& u, int64_t id0, float slack, hipStream_t s
 }  // namespace
 
 void mapupd_free(MapUpdBuf& u) {
-    void* bufs[] = {u.f64,   u.pos64, u.add_flag, u.pos,   u.cls,    u.world,    u.xyz_a,    u.xyz_b, u.pending,
-                    u.skey,  u.sval,  u.skey2,    u.sval2, u.xs,     u.vlist,    u.dlist,    u.tmp_cell, u.tmp_rank, u.tlist,
-                    u.hkey,  u.hhead, u.hend,     u.tmp,   u.cnt,    u.boxes, u.vnruns, u.runs, u.blk};
-    for (void* p : bufs)
-        if (p) (void)hipFree(p);
+    dev_free(&u.f64, &u.pos64, &u.add_flag, &u.pos, &u.cls, &u.world, &u.xyz_a, &u.xyz_b, &u.pending, &u.skey, &u.sval,
+             &u.skey2, &u.sval2, &u.xs, &u.vlist, &u.dlist, &u.tmp_cell, &u.tmp_rank, &u.tlist, &u.hkey, &u.hhead, &u.hend,
+             &u.tmp, &u.cnt, &u.boxes, &u.vnruns, &u.runs, &u.blk);
     if (u.h_cnt) (void)hipHostFree(u.h_cnt);
     u = MapUpdBuf{};
 }
@@ -1268,13 +1193,13 @@ int map_add_device(GridBuf& g, MapUpdBuf& u, const float* d_xyz, int64_t n64, bo
                    float slack, int64_t out[2], hipStream_t st) {
     out[0] = out[1] = 0;
     if (n64 <= 0) return 0;
-    if (n64 >= (int64_t)1 << 30) return -1;
+    if (n64 >= (int64_t)1 << 30) return kArg;
     const int n = (int)n64;
-    if (ensure_pts(u, n, st)) return -5;
+    if (const int rc = ensure_pts(u, n, st)) return rc;
     const int64_t id0 = g.n_ids;
     int rc = grid_reserve_ids(g, id0 + n, st);
     if (rc) return rc;
-    UPD_CHK(hipMemsetAsync(u.cnt, 0, 16 * sizeof(uint32_t), st));
+    LIO_HIP(hipMemsetAsync(u.cnt, 0, 16 * sizeof(uint32_t), st));
     rc = enqueue_grouped(g, u, d_xyz, nullptr, downsample ? kToAdd : kNoNeed, n, ds, id0, st);
     if (rc) return rc;
     rc = finish_add(g, u, id0, slack, st);
@@ -1284,7 +1209,7 @@ int map_add_device(GridBuf& g, MapUpdBuf& u, const float* d_xyz, int64_t n64, bo
         return rc;
     }
     // a voxel spread over more than kMaxRuns sort blocks: the globally sorted path
-    UPD_CHK(hipMemsetAsync(u.cnt, 0, 16 * sizeof(uint32_t), st));
+    LIO_HIP(hipMemsetAsync(u.cnt, 0, 16 * sizeof(uint32_t), st));
     zero_u32_kernel<<<(n + 1 + 255) / 256, 256, 0, st>>>(u.add_flag, n + 1);
     if (downsample) {
         set_u32_kernel<<<1, 1, 0, st>>>(u.cnt + kCAdd, (uint32_t)n);
@@ -1304,17 +1229,17 @@ int map_delete_boxes(GridBuf& g, MapUpdBuf& u, const float* boxes, int nb, float
                      hipStream_t st) {
     *n_deleted = 0;
     if (nb <= 0 || g.n_ids == 0) return 0;
-    if (ensure_pts(u, 1, st)) return -5;
+    if (const int rc = ensure_pts(u, 1, st)) return rc;
     if (!u.boxes || nb > u.boxes_cap) {
-        if (u.boxes) (void)hipFree(u.boxes);
-        UPD_CHK(hipMalloc(&u.boxes, (size_t)nb * 6 * sizeof(float)));
+        u.boxes_cap = 0;
+        if (dev_alloc_all({dev_req(u.boxes, (size_t)nb * 6)})) return kNoMem;
         u.boxes_cap = nb;
     }
-    UPD_CHK(hipMemcpyAsync(u.boxes, boxes, (size_t)nb * 6 * sizeof(float), hipMemcpyHostToDevice, st));
-    UPD_CHK(hipMemsetAsync(u.cnt, 0, 16 * sizeof(uint32_t), st));
+    LIO_HIP(hipMemcpyAsync(u.boxes, boxes, (size_t)nb * 6 * sizeof(float), hipMemcpyHostToDevice, st));
+    LIO_HIP(hipMemsetAsync(u.cnt, 0, 16 * sizeof(uint32_t), st));
     delete_boxes_kernel<<<(int)((g.n_ids + 255) / 256), 256, 0, st>>>(g.by_id, g.n_ids, u.boxes, nb, u.cnt + kCDead);
-    UPD_CHK(hipMemcpyAsync(u.h_cnt, u.cnt, 16 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    UPD_CHK(hipStreamSynchronize(st));
+    LIO_HIP(hipMemcpyAsync(u.h_cnt, u.cnt, 16 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    LIO_HIP(hipStreamSynchronize(st));
     *n_deleted = u.h_cnt[kCDead];
     if (*n_deleted == 0) return 0;
     return grid_rebuild(g, g.geom.cell, slack, st);  // bulk deletes (the local map moved): re-lay once
@@ -1335,21 +1260,21 @@ __global__ void mapupd_warm_kernel(uint32_t* __restrict__ p) {
 int mapupd_presize(MapUpdBuf& u, int64_t n, hipStream_t st) {
     if (n <= 0) return 0;
     mapupd_warm_kernel<<<1, 64, 0, st>>>(nullptr);
-    UPD_CHK(hipGetLastError());
-    if (n >= (int64_t)1 << 30) return -1;
-    if (ensure_pts(u, n, st)) return -5;
+    LIO_HIP(hipGetLastError());
+    if (n >= (int64_t)1 << 30) return kArg;
+    if (const int rc = ensure_pts(u, n, st)) return rc;
     size_t b1 = 0, b2 = 0, b3 = 0;
-    UPD_CHK(hipcub::DeviceScan::ExclusiveSum(nullptr, b1, u.add_flag, u.pos, (int)n + 1, st));
-    UPD_CHK(hipcub::DeviceScan::ExclusiveSum(nullptr, b2, u.f64, u.pos64, (int)n + 1, st));
-    UPD_CHK(hipcub::DeviceRadixSort::SortPairs(nullptr, b3, u.skey, u.skey2, u.sval, u.sval2, (int)n, 0, u.hbits + 1, st));
-    return ensure_tmp(u, std::max(b1, std::max(b2, b3))) ? -5 : 0;
+    LIO_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, b1, u.add_flag, u.pos, (int)n + 1, st));
+    LIO_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, b2, u.f64, u.pos64, (int)n + 1, st));
+    LIO_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, b3, u.skey, u.skey2, u.sval, u.sval2, (int)n, 0, u.hbits + 1, st));
+    return grow_scratch(&u.tmp, u.tmp_bytes, std::max(b1, std::max(b2, b3)));
 }
 
 int map_incremental(GridBuf& g, MapUpdBuf& u, IncrArgs a, float ds, float slack, int64_t out[4], hipStream_t st) {
     for (int k = 0; k < 4; ++k) out[k] = 0;
     const int n = a.n;
     if (n <= 0) return 0;
-    if (ensure_pts(u, n, st)) return -5;
+    if (const int rc = ensure_pts(u, n, st)) return rc;
     const int64_t id0 = g.n_ids;
     int rc = grid_reserve_ids(g, id0 + n, st);
     if (rc) return rc;
@@ -1360,7 +1285,7 @@ int map_incremental(GridBuf& g, MapUpdBuf& u, IncrArgs a, float ds, float slack,
     a.cls = u.cls;
     a.pending = u.pending;
     a.pending_count = reinterpret_cast<int*>(u.cnt + kCPend);
-    UPD_CHK(hipMemsetAsync(u.cnt, 0, 16 * sizeof(uint32_t), st));
+    LIO_HIP(hipMemsetAsync(u.cnt, 0, 16 * sizeof(uint32_t), st));
     const int nb = (n + 255) / 256;
     incr_classify_kernel<<<nb, 256, 0, st>>>(a);
     incr_pending_kernel<<<128, 256, 0, st>>>(a);
@@ -1370,9 +1295,10 @@ int map_incremental(GridBuf& g, MapUpdBuf& u, IncrArgs a, float ds, float slack,
     rc = finish_add(g, u, id0, slack, st);
     uint32_t n_add = u.h_cnt[kCAdd];
     if (rc == kRedo) {  // a voxel spread over more than kMaxRuns sort blocks: compact, then the sorted path
-        UPD_CHK(hipMemsetAsync(u.cnt, 0, 16 * sizeof(uint32_t), st));
+        LIO_HIP(hipMemsetAsync(u.cnt, 0, 16 * sizeof(uint32_t), st));
         incr_flags_kernel<<<(n + 1 + 255) / 256, 256, 0, st>>>(u.cls, n, u.f64, u.add_flag);
-        rc = exclusive_scan64(u, u.f64, u.pos64, n + 1, st);
+        rc = cub_exclusive_sum(u.tmp, u.tmp_bytes, kGrowScratch, static_cast<const unsigned long long*>(u.f64), u.pos64,
+                               n + 1, st);
         if (rc) return rc;
         incr_scatter_kernel<<<(n + 1 + 255) / 256, 256, 0, st>>>(u.world, u.cls, n, u.pos64, u.xyz_a, u.xyz_b, u.cnt);
         rc = enqueue_add(g, u, u.xyz_a, n, u.xyz_b, ds, id0, st);

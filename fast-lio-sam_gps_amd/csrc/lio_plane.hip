@@ -21,23 +21,13 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <string>
 
-#include "lio_error.hpp"
+#include "lio_scratch.hpp"
 #include "lio_plane.hpp"
 
 namespace lio {
 
 namespace {
-
-#define PCHK(x)                                                                    \
-    do {                                                                           \
-        const hipError_t e_ = (x);                                                 \
-        if (e_ != hipSuccess) {                                                    \
-            last_error() = std::string(#x) + ": " + hipGetErrorString(e_);         \
-            return -2;                                                             \
-        }                                                                          \
-    } while (0)
 
 using ull = unsigned long long;
 typedef float f2v __attribute__((ext_vector_type(2)));
@@ -47,8 +37,6 @@ constexpr int kTile = 1024;       // points staged in LDS at a time (12 KiB)
 constexpr int kChunk = 2048;      // points per workgroup: 2 M points x 1000 hypotheses = 3908 workgroups
 constexpr int kMomBlocks = 256;   // most workgroups of the moment reduction
 constexpr int kSelThreads = 1024;
-
-inline int nblk(int64_t n) { return (int)std::max<int64_t>(1, (n + 255) / 256); }
 
 // ---- the evaluation kernel ---------------------------------------------------------------------------
 // Thread = hypothesis (its plane in four registers), workgroup = 256 hypotheses x one chunk of points.  The
@@ -220,34 +208,29 @@ int plane_reserve(PlaneBuf& p, int64_t n, int64_t K) {
         count_alloc();
         if (hipHostMalloc(&p.h_pin, 256) != hipSuccess) {
             p.h_pin = nullptr;
-            return -5;
+            return kNoMem;
         }
     }
-    if (n <= p.cap_n && K <= p.cap_k && p.arena) return 0;
-    const int64_t cn = n <= p.cap_n ? p.cap_n : std::max<int64_t>(std::max<int64_t>(n, p.cap_n + p.cap_n / 2), 4096);
-    const int64_t ck = K <= p.cap_k ? p.cap_k : std::max<int64_t>(std::max<int64_t>(K, p.cap_k + p.cap_k / 2), 1024);
-    if (p.arena) (void)hipFree(p.arena);
-    p.arena = nullptr, p.cap_n = 0, p.cap_k = 0;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = off;
-        off += (bytes + 255) & ~(size_t)255;
-        return at;
-    };
+    if (n <= p.cap_n && K <= p.cap_k && p.arena) return kOk;
+    const int64_t cn = n <= p.cap_n ? p.cap_n : grown<int64_t>(n, p.cap_n, 4096);
+    const int64_t ck = K <= p.cap_k ? p.cap_k : grown<int64_t>(K, p.cap_k, 1024);
+    dev_free(&p.arena);
+    p.cap_n = 0, p.cap_k = 0;
     const size_t N = (size_t)cn, H = (size_t)ck;
-    const size_t o_planes = take(16 * H), o_cnt = take(8 * H), o_sq = take(8 * H), o_mask = take(N), o_inl = take(4 * N);
-    const size_t o_part = take(8 * 9 * kMomBlocks), o_mom = take(8 * 10), o_win = take(sizeof(PlaneWinner));
+    auto carve = [&](Carver at) {  // the arena's fields, once each, in arena order
+        at(p.planes, H), at(p.cnt, H), at(p.sq, H), at(p.mask, N), at(p.inliers, N);
+        at(p.part, 9 * kMomBlocks), at(p.mom, 10), at(p.win, 1);
+        return at.bytes();
+    };
+    const size_t total = carve(Carver{});
     count_alloc();
-    if (hipMalloc(&p.arena, off) != hipSuccess) {
+    if (hipMalloc(&p.arena, total) != hipSuccess) {
         p.arena = nullptr;
-        return -5;
+        return kNoMem;
     }
-    auto* a = static_cast<uint8_t*>(p.arena);
-    p.planes = (float4*)(a + o_planes), p.cnt = (ull*)(a + o_cnt), p.sq = (ull*)(a + o_sq);
-    p.mask = a + o_mask, p.inliers = (int32_t*)(a + o_inl);
-    p.part = (double*)(a + o_part), p.mom = (double*)(a + o_mom), p.win = (PlaneWinner*)(a + o_win);
+    carve(Carver{p.arena});
     p.cap_n = cn, p.cap_k = ck;
-    return 0;
+    return kOk;
 }
 
 // cyclic Jacobi on a symmetric 3 x 3 matrix: A becomes diagonal, the columns of V the eigenvectors
@@ -309,7 +292,7 @@ inline uint64_t mix64(uint64_t z) {  // splitmix64's output function
 }  // namespace
 
 void plane_free(PlaneBuf& p) {
-    if (p.arena) (void)hipFree(p.arena);
+    dev_free(&p.arena);
     if (p.h_pin) (void)hipHostFree(p.h_pin);
     p = PlaneBuf{};
 }
@@ -363,20 +346,20 @@ int segment_plane(DenoiseBuf& b, PlaneBuf& p, const float* d_pts, const float* h
     const float thr2 = thr * thr;
     if (n < 1 || n >= (int64_t)1 << 31 || K < 1 || K > (int64_t)1 << 20 || stride < 3 || stride > 8 || !(thr > 0.f) ||
         !std::isfinite(thr2) || (int64_t)p.h_planes.size() < 4 * K)
-        return -1;
+        return kArg;
     int rc = denoise_reserve(b, n);
     if (!rc) rc = plane_reserve(p, n, K);
     if (rc) return rc;
     int e = 0;
     (void)std::frexp(thr2, &e);
-    PCHK(hipMemcpyAsync(p.planes, p.h_planes.data(), (size_t)K * 16, hipMemcpyHostToDevice, st));
-    PCHK(hipMemsetAsync(p.cnt, 0, (size_t)K * 8, st));
-    PCHK(hipMemsetAsync(p.sq, 0, (size_t)K * 8, st));
+    LIO_HIP(hipMemcpyAsync(p.planes, p.h_planes.data(), (size_t)K * 16, hipMemcpyHostToDevice, st));
+    LIO_HIP(hipMemsetAsync(p.cnt, 0, (size_t)K * 8, st));
+    LIO_HIP(hipMemsetAsync(p.sq, 0, (size_t)K * 8, st));
     const dim3 grid((unsigned)((n + kChunk - 1) / kChunk), (unsigned)((K + kHypBlock - 1) / kHypBlock));
     pl_eval_kernel<<<grid, kHypBlock, 0, st>>>(d_pts, n, stride, p.planes, K, thr, 32 - e, p.cnt, p.sq);
     pl_select_kernel<<<1, kSelThreads, 0, st>>>(p.planes, p.cnt, p.sq, K, p.win);
     pl_flag_kernel<<<nblk(n + 1), 256, 0, st>>>(d_pts, n, stride, p.win, thr, b.flags, p.mask);
-    PCHK(hipMemcpyAsync(p.h_pin, p.win, sizeof(PlaneWinner), hipMemcpyDeviceToHost, st));
+    LIO_HIP(hipMemcpyAsync(p.h_pin, p.win, sizeof(PlaneWinner), hipMemcpyDeviceToHost, st));
     int64_t m = 0;
     if ((rc = dn_scan_count(b, n, &m, st))) return rc;  // waits: the winner is on the host too
     PlaneWinner w;
@@ -393,12 +376,12 @@ int segment_plane(DenoiseBuf& b, PlaneBuf& p, const float* d_pts, const float* h
             double* h_mom = reinterpret_cast<double*>(static_cast<uint8_t*>(p.h_pin) + 64);
             pl_moment_kernel<<<nb, 256, 0, st>>>(d_pts, stride, p.inliers, m, per, p.part);
             pl_moment_sum_kernel<<<1, kMomBlocks, 0, st>>>(p.part, nb, p.inliers, p.mom);
-            PCHK(hipMemcpyAsync(h_mom, p.mom, 10 * sizeof(double), hipMemcpyDeviceToHost, st));
-            PCHK(hipStreamSynchronize(st));
+            LIO_HIP(hipMemcpyAsync(h_mom, p.mom, 10 * sizeof(double), hipMemcpyDeviceToHost, st));
+            LIO_HIP(hipStreamSynchronize(st));
             plane_refit(h_mom, m, h_pts + (size_t)(int64_t)h_mom[9] * stride, w.plane, out->refit);
         }
     }
-    PCHK(hipGetLastError());
+    LIO_HIP(hipGetLastError());
     return 0;
 }
 

@@ -59,8 +59,8 @@ void plane_hypotheses(const float* pts, int stride, const int32_t* tri, int64_t 
 // Scores the K planes in p.h_planes (plane_hypotheses) against the n >= 1 records at d_pts (device; h_pts: the
 // same records on the host, read for the refit's reference point), selects the winner, flags, compacts and
 // takes the moments of its inliers.  Results on the device in p.cnt / p.sq (K), p.mask (n), p.inliers; the
-// rest in *out.  Waits for the stream.  Status: 0, -1 bad arguments, -2 HIP error (text in last_error()), -5
-// out of memory.
+// rest in *out.  Waits for the stream.  Status (lio_scratch.hpp): kOk, kArg, kHip (text in
+// last_error()), kNoMem.
 int segment_plane(DenoiseBuf& b, PlaneBuf& p, const float* d_pts, const float* h_pts, int64_t n, int stride, float thr,
                   int64_t K, bool want_refit, PlaneResult* out, hipStream_t st);
 

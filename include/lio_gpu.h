@@ -56,7 +56,7 @@ int lio_device_count(void);
 const char* lio_last_error(void);
 const char* lio_build_info(void);
 /* Diagnostics (no device needed): device / pinned allocations the library's growth paths (loop ICP, grids,
- * filters, scan buffers) have made in this process.  A warm loop-closure sequence adds none (bench.py
+ * filters, scan buffers, map updates) have made in this process.  A warm loop-closure sequence adds none (bench.py
  * loop_sequence).                                                                                  */
 int64_t lio_alloc_count(void);
 /* ABI guard (no device needed): sizeof of the public structs, in the order map_params, match_params, pose,
