@@ -349,6 +349,8 @@ struct lio_icp {
     int64_t hx_cap = 0;
     lio::PclBuf pg;
     int64_t fid_stats[4] = {0, 0, 0, 0};  // re-passes, serial fallbacks, events of the last pass, passes
+    float last_pcl16[16] = {};            // the last correspondence pass's float statistics (lio_icp_get_umeyama_stats)
+    bool have_pcl16 = false;
     int fid_flags = 0;
     int64_t fid_evcap = 0;
     bool timing = false;
@@ -738,7 +740,9 @@ static int icp_prepare(lio_icp* h) {
         if (h->h_super) (void)hipHostFree(h->h_super);
         h->h_super = nullptr;
         h->h_super_dev = nullptr;
-        const int64_t c = icp_cap(nsup_all, h->super_cap * lio::kIcpSuper) / lio::kIcpSuper + 1;
+        // icp_cap counts points: the records' points in, records out (with the record count in, every source got
+        // the floor's 129 records, and one above 129 * 4096 points had its last records written past the end)
+        const int64_t c = icp_cap(nsup_all * lio::kIcpSuper, h->super_cap * lio::kIcpSuper) / lio::kIcpSuper + 1;
         h->super_cap = 0;
         lio::count_alloc();
         IHIP(hipHostMalloc(&h->h_super, c * lio::kIcpStride * sizeof(double), hipHostMallocMapped));
@@ -1344,6 +1348,15 @@ extern "C" int lio_icp_get_fidelity_stats(lio_icp* h, int64_t* out4) {
     return LIO_OK;
 }
 
+extern "C" int lio_icp_get_umeyama_stats(lio_icp* h, float* out16) {
+    if (!h || !out16) return ifail(LIO_ERR_ARG, "lio_icp_get_umeyama_stats: bad arguments");
+    icp_join(h);
+    if (h->p.umeyama_float <= 0) return ifail(LIO_ERR_STATE, "lio_icp_get_umeyama_stats: the handle runs the double statistics");
+    if (!h->have_pcl16) return ifail(LIO_ERR_STATE, "lio_icp_get_umeyama_stats: no pass run yet");
+    std::memcpy(out16, h->last_pcl16, sizeof(h->last_pcl16));
+    return LIO_OK;
+}
+
 extern "C" int lio_icp_set_fidelity_debug(lio_icp* h, int flags, int64_t evcap) {
     if (!h || evcap < 0) return ifail(LIO_ERR_ARG, "lio_icp_set_fidelity_debug: bad arguments");
     icp_join(h);
@@ -1522,6 +1535,7 @@ int lio_icp_align(lio_icp* h, const float* guess16, lio_icp_result* out, float* 
         h->thist_cap = hist_need;
     }
     h->nT = 0;
+    h->have_pcl16 = false;
     h->have_prior = false;
     h->have_order = false;  // every alignment starts in cell order (its first pass measures the tiles)
     const double max_d2 = h->p.max_corr_dist * h->p.max_corr_dist;
@@ -1539,6 +1553,10 @@ int lio_icp_align(lio_icp* h, const float* guess16, lio_icp_result* out, float* 
         float pcl16[16];
         rc = icp_pass(h, false, apply, Tapply, max_d2, st, pcl_float ? pcl16 : nullptr);
         if (rc) return rc;
+        if (pcl_float) {
+            std::memcpy(h->last_pcl16, pcl16, sizeof(pcl16));
+            h->have_pcl16 = true;
+        }
         out->last_corr = (int64_t)st[0];
         if (st[0] < 3) {
             out->is_converged = 0;

@@ -62,20 +62,20 @@ DOUBLE_STATS = -1
 
 
 def icp_params(config: LoopClosureConfig, cell_size: float = 1.0, device: int = 0,
-               umeyama_float: int = FIDELITY_ORDER) -> _capi.IcpParams:
+               umeyama_float: int = FIDELITY_ORDER, max_iter: int = 50) -> _capi.IcpParams:
     # setTransformationEpsilon(0.01), setEuclideanFitnessEpsilon(0.01), setMaximumIterations(50)
-    return _capi.IcpParams(config.icp_max_corr_dist_, 0.01, 0.01, 50, 0.0, config.icp_score_threshold_,
+    return _capi.IcpParams(config.icp_max_corr_dist_, 0.01, 0.01, int(max_iter), 0.0, config.icp_score_threshold_,
                            cell_size, device, int(umeyama_float))
 
 
 class LoopClosure:
     def __init__(self, config: LoopClosureConfig, cell_size: float = 1.0, device: int = 0,
-                 umeyama_float: int = FIDELITY_ORDER):
+                 umeyama_float: int = FIDELITY_ORDER, max_iter: int = 50):
         """umeyama_float: 1..3 a float order of pcl::umeyama (default 2, the reference's arithmetic; sharded
         ranks all-gather their correspondence ids and give the one-rank transform bit for bit);
-        DOUBLE_STATS (-1) the opt-in double statistics."""
+        DOUBLE_STATS (-1) the opt-in double statistics.  max_iter: setMaximumIterations (frozen at create)."""
         self.config_ = config
-        self._p = icp_params(config, cell_size, device, umeyama_float)
+        self._p = icp_params(config, cell_size, device, umeyama_float, max_iter)
         self._h = C.c_void_p()
         check(lib().lio_icp_create(C.byref(self._p), C.byref(self._h)))
         self.aligned_ = np.zeros((0, 3), np.float32)
@@ -127,6 +127,13 @@ class LoopClosure:
         out = (C.c_int64 * 4)()
         check(lib().lio_icp_get_fidelity_stats(self._h, out))
         return dict(repasses=out[0], serial=out[1], events=out[2], passes=out[3])
+
+    def umeyama_stats(self) -> np.ndarray:
+        """the 16 floats the last correspondence pass handed to the host Umeyama (float orders only):
+        [sum src xyz, sum tgt xyz, count (uint32 bits), sigma 9 row-major target x source]"""
+        out = np.zeros(16, np.float32)
+        check(lib().lio_icp_get_umeyama_stats(self._h, out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
 
     def set_fidelity_debug(self, flags: int = 0, evcap: int = 0):
         check(lib().lio_icp_set_fidelity_debug(self._h, int(flags), int(evcap)))
@@ -267,9 +274,9 @@ class LoopClosureGroup:
     for bit."""
 
     def __init__(self, config: LoopClosureConfig, n_gpus: int, devices=None, cell_size: float = 1.0,
-                 umeyama_float: int = FIDELITY_ORDER):
+                 umeyama_float: int = FIDELITY_ORDER, max_iter: int = 50):
         self.config_ = config
-        self._p = icp_params(config, cell_size, 0 if devices is None else int(devices[0]), umeyama_float)
+        self._p = icp_params(config, cell_size, 0 if devices is None else int(devices[0]), umeyama_float, max_iter)
         self._h = C.c_void_p()
         devs = None
         if devices is not None:

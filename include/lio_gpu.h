@@ -329,6 +329,11 @@ int lio_icp_umeyama_pcl_float_order(const float* sums16, int order, float* T16);
  * re-compacts on the serial kernels and clears the flag); evcap > 0 caps the events per chain
  * (overflow -> the serial fallback).                                                              */
 int lio_icp_get_fidelity_stats(lio_icp* h, int64_t* out4);
+/* Test hook: the 16 floats of the last alignment's last correspondence pass (not the getFitnessScore pass),
+ * exactly as handed to the host Umeyama — the sums16 of lio_icp_umeyama_pcl_float_order; also valid when
+ * that pass ended with fewer than 3 pairs (state 5).  Sharded, every rank reports its own copy.
+ * LIO_ERR_STATE with the double statistics or before any pass has run.                            */
+int lio_icp_get_umeyama_stats(lio_icp* h, float* out16);
 int lio_icp_set_fidelity_debug(lio_icp* h, int flags, int64_t evcap);
 /* Test hook: sequential float sums of 6 interleaved chains (x: n x 6 host floats) on `device` through
  * the seqsum path — sums6[c] = fl(...fl(x[0][c] + x[1][c]) ... + x[n-1][c]); passes_out = passes used
