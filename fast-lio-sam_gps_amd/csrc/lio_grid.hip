@@ -10,6 +10,7 @@
 
 #include "lio_scratch_cub.hpp"
 #include "lio_grid_dev.hpp"
+#include "lio_grid_margin.hpp"
 #include "lio_kernels.hpp"
 
 namespace lio {
@@ -96,10 +97,15 @@ __global__ void __launch_bounds__(256) aabb_final_kernel(const float* __restrict
     if (threadIdx.x == 0) out[6] = __uint_as_float(s_cnt);
 }
 
-__global__ void init_by_id_kernel(const float* __restrict__ xyz, int64_t n, float4* __restrict__ by_id) {
+__global__ void init_by_id_kernel(const float* __restrict__ xyz, int64_t n, float4* __restrict__ by_id,
+                                  bool drop_nonfinite) {
     const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     if (i >= n) return;
-    by_id[i] = make_float4(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], 1.f);
+    // map grids: a row that is not finite takes its id but is stored deleted — no part of the AABB, nobody's
+    // neighbour (the loop ICP's callers filter their clouds: its grids keep every row)
+    const float x = xyz[3 * i], y = xyz[3 * i + 1], z = xyz[3 * i + 2];
+    const bool dead = drop_nonfinite && !(isfinite(x) && isfinite(y) && isfinite(z));
+    by_id[i] = make_float4(x, y, z, dead ? 0.f : 1.f);
 }
 
 // keys of every id; dead ids get the sentinel ncells (sorted past the table)
@@ -270,8 +276,8 @@ GridDev grid_view(const GridBuf& g) {
     v.oz = g.geom.oz;
     v.cell = g.geom.cell;
     v.inv_cell = 1.0f / g.geom.cell;
-    // assignment uses floorf((v - o) * inv): error << 1e-3 m for |v| < 1e4 m
-    v.margin = 1e-3f + 1e-4f * g.geom.cell;
+    // covers the rounding of the computed faces against floorf((v - o) * inv) at any offset and extent
+    v.margin = grid_margin(g.geom);
     v.nx = g.geom.nx;
     v.ny = g.geom.ny;
     v.nz = g.geom.nz;
@@ -347,7 +353,7 @@ int grid_build(GridBuf& g, const float* d_xyz, int64_t n, float cell, hipStream_
     if (rc) return rc;
     rc = reserve_entries(g, room);
     if (rc) return rc;
-    init_by_id_kernel<<<(int)((n + 255) / 256), 256, 0, st>>>(d_xyz, n, g.by_id);
+    init_by_id_kernel<<<(int)((n + 255) / 256), 256, 0, st>>>(d_xyz, n, g.by_id, g.gapped);
     g.n_ids = n;
     return grid_rebuild(g, cell, 0.f, st);
 }

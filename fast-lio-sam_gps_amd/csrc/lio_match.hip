@@ -440,7 +440,10 @@ __global__ void __launch_bounds__(256) map_knn_kernel(GridDev g, const float* __
     if (i >= n) return;
     TopK<5> tk;
     tk.init(bound);
-    group_knn_exact<5, G>(g, q[3 * (size_t)i], q[3 * (size_t)i + 1], q[3 * (size_t)i + 2], max_shell, sub, tk);
+    const float qx = q[3 * (size_t)i], qy = q[3 * (size_t)i + 1], qz = q[3 * (size_t)i + 2];
+    // a query that is not finite has no neighbours (group-uniform: the whole group skips the walk, which
+    // would otherwise visit every shell, and for an infinite query accept every point at d2 = inf)
+    if (isfinite(qx) && isfinite(qy) && isfinite(qz)) group_knn_exact<5, G>(g, qx, qy, qz, max_shell, sub, tk);
     if (sub < k) {
         int v = tk.id(0);
         float d = tk.d(0);

@@ -87,7 +87,9 @@ int lio_map_destroy(lio_map* m);
  * value <= 0 keeps the current one); only while the map holds no points, so
  * every lio_ctx already created on m stays valid.  device must not change. */
 int lio_map_set_params(lio_map* m, const lio_map_params* p);
-/* ikdtree.Build(points) [U]: replaces the content. xyz: n*3 float, host.   */
+/* ikdtree.Build(points) [U]: replaces the content. xyz: n*3 float, host.
+ * A row with a NaN or infinite coordinate keeps its id but is stored as a
+ * deleted one: it is no part of the grid and nobody's neighbour.           */
 int lio_map_build(lio_map* m, const float* xyz, int64_t n);
 /* same, xyz already resident in device memory (e.g. a torch tensor).       */
 int lio_map_build_device(lio_map* m, const float* d_xyz, int64_t n);
@@ -105,7 +107,8 @@ int lio_map_get_by_id(lio_map* m, float* xyz_out, uint8_t* alive_out);
  * points q (n*3 float): the k <= 5 nearest alive map points in ascending
  * (sq-distance, id) order with sq-distance <= max_dist^2 (max_dist <= 0 or
  * INFINITY: unbounded).  idx (n*k, map ids = insertion order, -1 where fewer
- * exist), d2 (n*k, optional, INFINITY where missing).                      */
+ * exist), d2 (n*k, optional, INFINITY where missing).  A query that is not
+ * finite has no neighbours.                                                 */
 int lio_map_nearest_search(lio_map* m, const float* q, int64_t n, int k, float max_dist, int32_t* idx, float* d2);
 /* Coordinates of map ids (Nearest_Points from lio_map_nearest_search /
  * lio_get_knn ids): xyz_out n*3; ids < 0 or unknown give NaN.             */
