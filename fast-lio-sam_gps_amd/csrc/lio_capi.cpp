@@ -23,6 +23,7 @@
 #include "lio_filter.hpp"
 #include "lio_denoise.hpp"
 #include "lio_cluster.hpp"
+#include "lio_dbscan.hpp"
 #include "lio_plane.hpp"
 #include "lio_pool.hpp"
 #include "lio_mapupd.hpp"
@@ -1072,7 +1073,7 @@ struct lio_filter {
     lio::ImuPose* d_poses = nullptr;
     int64_t poses_cap = 0;
     lio::DenoiseBuf dn;  // lio_sor_filter / lio_radius_first_seed / lio_denoise_slam_map
-    lio::ClusterBuf cl;  // lio_euclidean_clusters (with dn: the grid, the sorts and the scan)
+    lio::ClusterBuf cl;  // lio_euclidean_clusters, lio_dbscan (with dn: the grid, the sorts and the scan)
     lio::PlaneBuf pl;    // lio_segment_plane (with dn: the flags and the scan)
 };
 
@@ -1431,6 +1432,45 @@ int lio_euclidean_clusters(lio_filter* f, const float* pts, int64_t n, int strid
     if (stats4_opt)
         stats4_opt[0] = cc.finite, stats4_opt[1] = cc.components, stats4_opt[2] = cc.clusters,
         stats4_opt[3] = cc.clustered_points;
+    return LIO_OK;
+}
+
+// ---- DBSCAN with core flags and per-cluster bounding boxes (lio_dbscan.hip) ----
+int lio_dbscan(lio_filter* f, const float* pts, int64_t n, int stride, float eps, int64_t min_samples,
+               int32_t* labels_out, uint8_t* core_opt, int64_t* n_clusters, int64_t cap_clusters,
+               int64_t* offsets_opt, int32_t* indices_opt, float* aabb6_opt, int64_t* stats4_opt) {
+    int rc = denoise_handle(f, "lio_dbscan");
+    if (rc) return rc;
+    if (!n_clusters || n < 0 || n >= (int64_t)1 << 31 || (n > 0 && (!pts || !labels_out)) || stride < 3 ||
+        stride > lio::kMaxFields || !(eps > 0.f) || !std::isfinite(eps) || min_samples < 1 || cap_clusters < 0)
+        return fail(LIO_ERR_ARG, "lio_dbscan: bad arguments");
+    *n_clusters = 0;
+    if (stats4_opt)
+        for (int k = 0; k < 4; ++k) stats4_opt[k] = 0;
+    if (offsets_opt) offsets_opt[0] = 0;
+    if (n == 0) return LIO_OK;
+    HIP_TRY(hipSetDevice(f->dev));
+    rc = grow(&f->d_in, f->in_cap, n * stride);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(f->d_in, pts, (size_t)n * stride * sizeof(float), hipMemcpyHostToDevice, f->st));
+    lio::DbscanCounts dc;
+    rc = lio::dbscan(f->dn, f->cl, f->d_in, n, stride, eps, min_samples, cap_clusters, &dc, f->st);
+    if (rc) return status(rc, "lio_dbscan");
+    const int64_t m = std::min(dc.clusters, cap_clusters);
+    HIP_TRY(hipMemcpyAsync(labels_out, f->cl.labels, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, f->st));
+    if (core_opt) HIP_TRY(hipMemcpyAsync(core_opt, f->cl.rank_of, (size_t)n, hipMemcpyDeviceToHost, f->st));
+    if (indices_opt && dc.clustered_points)
+        HIP_TRY(hipMemcpyAsync(indices_opt, f->cl.indices, (size_t)dc.clustered_points * sizeof(int32_t),
+                               hipMemcpyDeviceToHost, f->st));
+    if (offsets_opt)
+        HIP_TRY(hipMemcpyAsync(offsets_opt, f->cl.offsets, (size_t)(m + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, f->st));
+    if (aabb6_opt && m)
+        HIP_TRY(hipMemcpyAsync(aabb6_opt, f->cl.aabb, (size_t)m * 6 * sizeof(float), hipMemcpyDeviceToHost, f->st));
+    HIP_TRY(hipStreamSynchronize(f->st));
+    *n_clusters = dc.clusters;
+    if (stats4_opt)
+        stats4_opt[0] = dc.finite, stats4_opt[1] = dc.core, stats4_opt[2] = dc.clusters,
+        stats4_opt[3] = dc.clustered_points;
     return LIO_OK;
 }
 

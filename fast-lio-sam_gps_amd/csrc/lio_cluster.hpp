@@ -30,6 +30,9 @@ struct ClusterCounts {
 };
 
 void cluster_free(ClusterBuf& c);
+// every buffer sized for n points (lio_dbscan.hip shares the arena: parents, run tables, labels, indices, offsets,
+// boxes; `rank_of` holds its core flags per input point)
+int cluster_reserve(ClusterBuf& c, int64_t n);
 // Clusters of the n records at d_pts (device; x, y, z first).  Results on the device in c.labels (n), c.indices
 // (the accepted points in cluster order), and for the first min(clusters, cap_clusters) clusters c.offsets
 // (+ 1 entry) and c.aabb; the counts on the host.  Waits for the stream twice (the component count, then the

@@ -47,7 +47,7 @@ EXPORTS = [
     "lio_shm_exchange_open", "lio_shm_exchange_allgather", "lio_shm_exchange_close", "lio_shm_exchange_set_timeout",
     "lio_seq_shard_offsets", "lio_seq_shard_merge",
     "lio_sor_filter", "lio_radius_first_seed", "lio_denoise_slam_map", "lio_euclidean_clusters",
-    "lio_segment_plane", "lio_plane_sample_triples",
+    "lio_segment_plane", "lio_plane_sample_triples", "lio_dbscan",
 ]
 
 
@@ -214,6 +214,9 @@ def _declare(L):
         "lio_euclidean_clusters": (C.c_int, [vp, fp, C.c_int64, C.c_int, C.c_float, C.c_int64, C.c_int64,
                                              C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.c_int64,
                                              C.POINTER(C.c_int64), C.POINTER(C.c_int32), fp, C.POINTER(C.c_int64)]),
+        "lio_dbscan": (C.c_int, [vp, fp, C.c_int64, C.c_int, C.c_float, C.c_int64, C.POINTER(C.c_int32),
+                                 C.POINTER(C.c_uint8), C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_int64),
+                                 C.POINTER(C.c_int32), fp, C.POINTER(C.c_int64)]),
         "lio_segment_plane": (C.c_int, [vp, fp, C.c_int64, C.c_int, C.c_float, C.c_int, C.c_int64, C.c_uint64,
                                         C.POINTER(C.c_int32), fp, C.POINTER(C.c_int64), C.POINTER(C.c_int32),
                                         C.POINTER(C.c_int64), C.POINTER(C.c_uint8), C.POINTER(C.c_int64),

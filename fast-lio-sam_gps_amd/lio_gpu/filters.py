@@ -12,6 +12,8 @@
   end's intensity denoise (fast_lio_sam.cpp:941-1008, 575-646, 332-365) and its parts
 * :class:`EuclideanClusterExtraction` — ``pcl::EuclideanClusterExtraction`` with one axis-aligned bounding
   box per cluster (fast_lio_sam.cpp:343-363, post_process/clustering.py:39-75)
+* :class:`DBSCAN` — the offline pipeline's other clustering method (post_process/clustering.py:30-36), with
+  core flags and one box per cluster
 
 Point records are float rows ``[x, y, z, attr...]`` (3..8 floats); PCL's
 PointXYZI is ``stride = 4``, FAST-LIO's PointXYZINormal-with-time is
@@ -199,6 +201,57 @@ class EuclideanClusterExtraction(_Handle):
         return [self.indices[self.offsets[t]:self.offsets[t + 1]] for t in range(k)]
 
 
+class DBSCAN(_Handle):
+    """DBSCAN as the offline pipeline's ``cluster_with_dbscan`` calls it (post_process/clustering.py:30-36), by
+    the contract of ``lio_dbscan``: finite points are neighbours when their float squared distance is
+    ``<= eps * eps`` (inclusive, itself counted), a point with ``min_samples`` neighbours is core, a cluster is a
+    connected component of the core points, numbered by its lowest core index; a border point takes the
+    lowest-numbered cluster among its core neighbours'; everything else is noise (-1).  The defaults are
+    scikit-learn's (0.5, 5); the reference's call uses 0.5, 10.
+    After :meth:`fit`: ``labels_``, ``core_sample_indices_`` (scikit-learn's names), ``n_clusters``, ``offsets`` /
+    ``indices`` (cluster k is ``indices[offsets[k]:offsets[k + 1]]``), ``aabb`` (per cluster min x, y, z, max x, y,
+    z over all members) and ``stats`` = finite points, core points, clusters, clustered points."""
+
+    def __init__(self, eps: float = 0.5, min_samples: int = 5, device: int = 0):
+        super().__init__(device)
+        self.eps = float(eps)
+        self.min_samples = int(min_samples)
+        self.n_clusters = 0  # clusters of the last fit(), whatever its cap_clusters
+        self.labels_ = np.zeros(0, np.int32)
+        self.core_sample_indices_ = np.zeros(0, np.int64)
+        self.offsets = np.zeros(1, np.int64)
+        self.indices = np.zeros(0, np.int32)
+        self.aabb = np.zeros((0, 6), np.float32)
+        self.stats = np.zeros(4, np.int64)
+
+    def fit(self, pts: np.ndarray, cap_clusters: int | None = None) -> list:
+        """The list of index arrays.  ``cap_clusters`` (default: as many as there can be) bounds the clusters
+        that ``offsets`` / ``aabb`` and the returned list describe; ``labels_``, ``core_sample_indices_``,
+        ``indices`` and ``stats`` are always complete."""
+        pts2 = _rows(pts)
+        n = len(pts2)
+        cap = n if cap_clusters is None else int(cap_clusters)
+        labels = np.full(n, -1, np.int32)
+        core = np.zeros(n, np.uint8)
+        offsets = np.zeros(max(cap, 0) + 1, np.int64)
+        indices = np.zeros(n, np.int32)
+        aabb = np.zeros((max(cap, 0), 6), np.float32)
+        stats = np.zeros(4, np.int64)
+        m = C.c_int64(0)
+        i32p, i64p = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+        check(lib().lio_dbscan(self._h, _fp(pts2), n, pts2.shape[1], self.eps, self.min_samples,
+                               labels.ctypes.data_as(i32p), core.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(m), cap,
+                               offsets.ctypes.data_as(i64p), indices.ctypes.data_as(i32p), _fp(aabb),
+                               stats.ctypes.data_as(i64p)))
+        k = min(m.value, cap)
+        self.n_clusters = m.value
+        self.labels_, self.stats = labels, stats
+        self.core_sample_indices_ = np.flatnonzero(core).astype(np.int64)
+        self.offsets, self.aabb = offsets[: k + 1].copy(), aabb[:k].copy()
+        self.indices = indices[: stats[3]].copy()
+        return [self.indices[self.offsets[t]:self.offsets[t + 1]] for t in range(k)]
+
+
 def sample_triples(seed: int, n: int, num_iterations: int) -> np.ndarray:
     """The built-in sampler of :class:`PlaneSegmentation` (``lio_plane_sample_triples``; host only):
     ``num_iterations`` triples of distinct indices in ``[0, n)``; none for ``n < 3``."""
@@ -257,13 +310,18 @@ class PlaneSegmentation(_Handle):
 
 
 def cluster_objects(pts, nb_neighbors=20, std_ratio=2.0, distance_threshold=0.2, num_iterations=1000, seed=0,
-                    tolerance=0.5, min_size=10, max_size=10000):
+                    tolerance=0.5, min_size=10, max_size=10000, method="euclidean", min_samples=10):
     """The main block of post_process/clustering.py (:77-118) on one handle's worth of device work: statistical
     outlier removal, ground-plane segmentation, the plane's inliers dropped, Euclidean clustering, one bounding
     box per cluster.  Every stage is this library's (the outlier removal with PCL's semantics, the plane by the
     contract of ``lio_segment_plane``, the clusters as PCL's).  Returns a dict: ``clusters`` (index arrays into the rows of ``pts``), ``aabb`` (per
     cluster min x, y, z, max x, y, z), ``plane`` (a, b, c, d), ``ground`` (rows of ``pts`` on the plane) and
-    ``kept`` (rows of ``pts`` that passed the outlier removal)."""
+    ``kept`` (rows of ``pts`` that passed the outlier removal).
+    ``method="dbscan"`` (the script's other ``clustering_method``, :95-107) runs ``DBSCAN(tolerance, min_samples)``
+    in place of the Euclidean stage — ``min_size`` / ``max_size`` are not used then — and adds ``noise``: the rows
+    of ``pts`` that reached the clustering and were left in no cluster."""
+    if method not in ("euclidean", "dbscan"):
+        raise ValueError("cluster_objects: method must be 'euclidean' or 'dbscan'")
     pts2 = _rows(pts)
     sor = StatisticalOutlierRemoval(nb_neighbors, std_ratio)
     filtered = sor.filter(pts2)
@@ -276,6 +334,13 @@ def cluster_objects(pts, nb_neighbors=20, std_ratio=2.0, distance_threshold=0.2,
     plane, inl = seg.segment_plane(filtered, distance_threshold, 3, num_iterations, seed)
     seg.close()
     rest = np.flatnonzero(seg.mask == 0) if len(filtered) else np.zeros(0, np.int64)
+    if method == "dbscan":
+        db = DBSCAN(tolerance, min_samples)
+        found = db.fit(filtered[rest])
+        db.close()
+        rows = kept[rest]
+        return dict(clusters=[rows[c] for c in found], aabb=db.aabb, plane=plane, ground=kept[inl], kept=kept,
+                    noise=rows[db.labels_ < 0])
     ec = EuclideanClusterExtraction(tolerance, min_size, max_size)
     found = ec.extract(filtered[rest])
     ec.close()

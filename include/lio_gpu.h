@@ -547,6 +547,37 @@ int lio_euclidean_clusters(lio_filter* f, const float* pts, int64_t n, int strid
                            int64_t max_size, int32_t* labels_out, int64_t* n_clusters, int64_t cap_clusters,
                            int64_t* offsets_opt, int32_t* indices_opt, float* aabb6_opt, int64_t* stats4_opt);
 
+/* DBSCAN with one core flag per point and one axis-aligned bounding box per cluster: the second clustering
+ * method of the offline pipeline (post_process/clustering.py:30-36, cluster_with_dbscan: eps 0.5, min_samples
+ * 10), scikit-learn's DBSCAN [U] restated as sets.  pts is n x stride floats (x, y, z first; stride 3..8),
+ * 0 <= n < 2^31; eps finite and > 0; min_samples >= 1.  No float contraction, as everywhere in the library.
+ *   neighbour finite points i and j (j = i included) are neighbours when float ((dx*dx + dy*dy) + dz*dz) <= e2,
+ *             e2 = (float)((double)eps * eps).  THE TEST IS INCLUSIVE: a pair at exactly eps is a pair of
+ *             neighbours (DBSCAN's definition and scikit-learn's radius_neighbors), unlike the strict < of
+ *             lio_euclidean_clusters and lio_radius_first_seed, which follow PCL;
+ *   core      a finite point is core when it has >= min_samples neighbours, itself counted;
+ *   cluster   a connected component of the neighbour graph restricted to core points.  CLUSTERS ARE NUMBERED BY
+ *             THEIR LOWEST CORE INDEX, ASCENDING (scikit-learn opens clusters in index order at unlabelled core
+ *             points and expands each fully; stated here as this library's contract);
+ *   border    a finite non-core point with at least one core neighbour takes THE LOWEST-NUMBERED CLUSTER AMONG
+ *             ITS CORE NEIGHBOURS' CLUSTERS (the cluster that reaches it first; this library's contract) and
+ *             spreads the cluster no further;
+ *   noise     every other finite point and every non-finite point: label -1.  A non-finite point is nobody's
+ *             neighbour.  There is no size filter.
+ * labels_out (n): the number of the point's cluster, -1 for noise.  core_opt (n, may be NULL): 1 for a core
+ * point, else 0.  *n_clusters: the clusters.  indices_opt (n, may be NULL): all clustered points in cluster
+ * order, indices ascending inside a cluster.  offsets_opt (cap_clusters + 1, may be NULL) and aabb6_opt
+ * (6 x cap_clusters, may be NULL: float min x, y, z, max x, y, z over all members, border points included) are
+ * filled for the first min(*n_clusters, cap_clusters) clusters (offsets: one entry more, the end of the last of
+ * them); cap_clusters = 0 with NULLs is the "count only" call.  stats4_opt (may be NULL) = finite points, core
+ * points, clusters, clustered points; the noise among the finite points is [0] - [3].
+ * LIO_ERR_ARG before any device work: eps non-finite or <= 0, min_samples < 1, stride outside 3..8, n < 0 or
+ * n >= 2^31, cap_clusters < 0, NULL n_clusters, NULL pts or labels_out with n > 0.  Repeated calls and any
+ * scheduling of the device give identical results.                                                          */
+int lio_dbscan(lio_filter* f, const float* pts, int64_t n, int stride, float eps, int64_t min_samples,
+               int32_t* labels_out, uint8_t* core_opt, int64_t* n_clusters, int64_t cap_clusters,
+               int64_t* offsets_opt, int32_t* indices_opt, float* aabb6_opt, int64_t* stats4_opt);
+
 /* RANSAC plane segmentation: Open3D's PointCloud::SegmentPlane [U] as the offline pipeline calls it for ground
  * removal (post_process/clustering.py:21-28: distance_threshold 0.2, ransac_n 3, num_iterations 1000), restated
  * as a contract of this library (Open3D's std::mt19937 sampling and the float sum behind its RMSE tie-break

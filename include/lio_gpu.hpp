@@ -657,6 +657,55 @@ private:
     int64_t stats_[4] = {0, 0, 0, 0};
 };
 
+// DBSCAN as the offline pipeline calls it (post_process/clustering.py:30-36), in the shape of
+// EuclideanClusterExtraction: setInputCloud / setEps / setMinSamples / extract.  A pair at exactly eps is a pair
+// of neighbours (inclusive test); clusters are numbered by their lowest core index, a border point takes the
+// lowest-numbered cluster among its core neighbours' (lio_gpu.h); indices ascend inside a cluster and there is no
+// size filter.  The defaults are scikit-learn's: eps 0.5, min_samples 5.
+template <typename PointT>
+class DBSCAN {
+public:
+    explicit DBSCAN(FilterGPU& f) : f_(f) {}
+    void setInputCloud(const std::vector<PointT>* cloud) { in_ = cloud; }
+    void setEps(double eps) { eps_ = eps; }
+    void setMinSamples(int64_t min_samples) { min_samples_ = min_samples; }
+    void extract(std::vector<PointIndices>& clusters) {
+        if (!in_) throw Error(LIO_ERR_ARG, "DBSCAN: no input cloud");
+        const int64_t n = (int64_t)in_->size();
+        labels_.assign((size_t)n, -1);
+        core_.assign((size_t)n, 0);
+        std::vector<int32_t> idx((size_t)n);
+        std::vector<int64_t> off((size_t)n + 1, 0);
+        std::vector<float> box(6 * (size_t)n);
+        int64_t m = 0;
+        check(lio_dbscan(f_.handle(), reinterpret_cast<const float*>(in_->data()), n, float_stride<PointT>(), (float)eps_,
+                         min_samples_, labels_.data(), core_.data(), &m, n, off.data(), idx.data(), box.data(), stats_),
+              "DBSCAN::extract");
+        clusters.assign((size_t)m, PointIndices{});
+        aabbs_.resize((size_t)m);
+        for (int64_t k = 0; k < m; ++k) {
+            clusters[(size_t)k].indices.assign(idx.begin() + off[(size_t)k], idx.begin() + off[(size_t)k + 1]);
+            std::memcpy(&aabbs_[(size_t)k], &box[6 * (size_t)k], sizeof(ClusterAABB));
+        }
+    }
+    // of the last extract(): per input point its cluster (-1: noise) and 1 where it is a core point; one box per
+    // cluster; finite points, core points, clusters, clustered points
+    const std::vector<int32_t>& labels() const { return labels_; }
+    const std::vector<uint8_t>& core() const { return core_; }
+    const std::vector<ClusterAABB>& aabbs() const { return aabbs_; }
+    const int64_t* stats() const { return stats_; }
+
+private:
+    FilterGPU& f_;
+    const std::vector<PointT>* in_ = nullptr;
+    double eps_ = 0.5;  // scikit-learn's defaults
+    int64_t min_samples_ = 5;
+    std::vector<int32_t> labels_;
+    std::vector<uint8_t> core_;
+    std::vector<ClusterAABB> aabbs_;
+    int64_t stats_[4] = {0, 0, 0, 0};
+};
+
 // Open3D's PointCloud::SegmentPlane as the offline pipeline calls it (post_process/clustering.py:21-28), in the
 // shape of pcl::SACSegmentation: setInputCloud / setDistanceThreshold / setMaxIterations / setSeed / segment.
 // Every hypothesis is evaluated; the winner minimises (-inliers, fixed-point squared error, hypothesis index)
