@@ -1288,6 +1288,14 @@ int lio_filter_destroy(lio_filter* f) {
     return LIO_OK;
 }
 
+// the upload the filter entries open with: `floats` floats at `host` into f->d_in, grown to hold them
+static int upload_in(lio_filter* f, const float* host, int64_t floats) {
+    const int rc = grow(&f->d_in, f->in_cap, floats);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(f->d_in, host, (size_t)floats * sizeof(float), hipMemcpyHostToDevice, f->st));
+    return LIO_OK;
+}
+
 int lio_voxel_grid(lio_filter* f, const float* pts, int64_t n, int stride, const float leaf[3], float* out,
                    int64_t* n_out) {
     if (!f || !leaf || !n_out || n < 0 || (n > 0 && (!pts || !out)) || stride < 3 || stride > lio::kMaxFields ||
@@ -1296,10 +1304,9 @@ int lio_voxel_grid(lio_filter* f, const float* pts, int64_t n, int stride, const
     *n_out = 0;
     if (n == 0) return LIO_OK;
     HIP_TRY(hipSetDevice(f->dev));
-    int rc = grow(&f->d_in, f->in_cap, n * stride);
-    if (!rc) rc = grow(&f->d_out, f->out_cap, n * stride);
+    int rc = grow(&f->d_out, f->out_cap, n * stride);
+    if (!rc) rc = upload_in(f, pts, n * stride);
     if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(f->d_in, pts, (size_t)n * stride * sizeof(float), hipMemcpyHostToDevice, f->st));
     int64_t m = 0;
     rc = lio::voxel_grid(f->b, f->d_in, n, stride, leaf, f->d_out, &m, f->st);
     if (rc) return status(rc, "lio_voxel_grid");
@@ -1328,10 +1335,9 @@ int lio_sor_filter(lio_filter* f, const float* pts, int64_t n, int stride, int m
     *n_out = 0;
     HIP_TRY(hipSetDevice(f->dev));
     if (n > 0) {
-        rc = grow(&f->d_in, f->in_cap, n * stride);
-        if (!rc) rc = grow(&f->d_out, f->out_cap, n * stride);
+        rc = grow(&f->d_out, f->out_cap, n * stride);
+        if (!rc) rc = upload_in(f, pts, n * stride);
         if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(f->d_in, pts, (size_t)n * stride * sizeof(float), hipMemcpyHostToDevice, f->st));
     }
     int64_t m = 0;
     rc = lio::sor_filter(f->dn, f->d_in, n, stride, mean_k, stddev_mul, negative != 0, f->d_out, &m, distances_opt,
@@ -1353,11 +1359,9 @@ int lio_radius_first_seed(lio_filter* f, const float* pts, int64_t n, int stride
         return fail(LIO_ERR_ARG, "lio_radius_first_seed: bad arguments");
     if (n == 0) return LIO_OK;
     HIP_TRY(hipSetDevice(f->dev));
-    rc = grow(&f->d_in, f->in_cap, n * stride);
-    if (rc) return rc;
     rc = lio::denoise_reserve(f->dn, std::max(n, ns));
     if (rc) return status(rc, "lio_radius_first_seed");
-    HIP_TRY(hipMemcpyAsync(f->d_in, pts, (size_t)n * stride * sizeof(float), hipMemcpyHostToDevice, f->st));
+    if ((rc = upload_in(f, pts, n * stride))) return rc;
     if (ns) HIP_TRY(hipMemcpyAsync(f->dn.seeds_xyz, seeds_xyz, (size_t)ns * 3 * sizeof(float), hipMemcpyHostToDevice, f->st));
     rc = lio::radius_first_seed(f->dn, f->d_in, n, stride, f->dn.seeds_xyz, ns, radius, f->dn.seed_id, f->dn.seed_d2,
                                 f->st);
@@ -1382,10 +1386,9 @@ int lio_denoise_slam_map(lio_filter* f, const float* pts, int64_t n, const lio_d
         for (int k = 0; k < 5; ++k) counts5_opt[k] = 0;
     if (n == 0) return LIO_OK;
     HIP_TRY(hipSetDevice(f->dev));
-    rc = grow(&f->d_in, f->in_cap, n * 4);
-    if (!rc) rc = grow(&f->d_out, f->out_cap, n * 4);
+    rc = grow(&f->d_out, f->out_cap, n * 4);
+    if (!rc) rc = upload_in(f, pts, n * 4);
     if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(f->d_in, pts, (size_t)n * 4 * sizeof(float), hipMemcpyHostToDevice, f->st));
     const lio::DenoiseParams dp{p->seed_thres,  p->cluster_seed_radius, p->denoise_radius,
                                 p->noise_thres, p->mean_k,              p->stddev_mul};
     int64_t m = 0;
@@ -1397,81 +1400,71 @@ int lio_denoise_slam_map(lio_filter* f, const float* pts, int64_t n, const lio_d
     return LIO_OK;
 }
 
-// ---- Euclidean cluster extraction with per-cluster bounding boxes (lio_cluster.hip) ----
-int lio_euclidean_clusters(lio_filter* f, const float* pts, int64_t n, int stride, float tolerance, int64_t min_size,
-                           int64_t max_size, int32_t* labels_out, int64_t* n_clusters, int64_t cap_clusters,
-                           int64_t* offsets_opt, int32_t* indices_opt, float* aabb6_opt, int64_t* stats4_opt) {
-    int rc = denoise_handle(f, "lio_euclidean_clusters");
+// ---- Euclidean cluster extraction and DBSCAN, both with per-cluster bounding boxes (lio_cluster.hip, lio_dbscan.hip) ----
+// what both entries open with: the argument check (r: tolerance / eps; least: min_size / min_samples), the
+// outputs of a call that finds nothing, the device and the upload.  The caller is done when this fails or n == 0.
+static int cluster_begin(lio_filter* f, const char* what, const float* pts, int64_t n, int stride, float r, int64_t least,
+                         const int32_t* labels_out, int64_t* n_clusters, int64_t cap_clusters, int64_t* offsets_opt,
+                         int64_t* stats4_opt) {
+    const int rc = denoise_handle(f, what);
     if (rc) return rc;
     if (!n_clusters || n < 0 || n >= (int64_t)1 << 31 || (n > 0 && (!pts || !labels_out)) || stride < 3 ||
-        stride > lio::kMaxFields || !(tolerance > 0.f) || !std::isfinite(tolerance) || min_size < 1 || cap_clusters < 0)
-        return fail(LIO_ERR_ARG, "lio_euclidean_clusters: bad arguments");
+        stride > lio::kMaxFields || !(r > 0.f) || !std::isfinite(r) || least < 1 || cap_clusters < 0)
+        return fail(LIO_ERR_ARG, std::string(what) + ": bad arguments");
     *n_clusters = 0;
     if (stats4_opt)
         for (int k = 0; k < 4; ++k) stats4_opt[k] = 0;
     if (offsets_opt) offsets_opt[0] = 0;
     if (n == 0) return LIO_OK;
     HIP_TRY(hipSetDevice(f->dev));
-    rc = grow(&f->d_in, f->in_cap, n * stride);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(f->d_in, pts, (size_t)n * stride * sizeof(float), hipMemcpyHostToDevice, f->st));
-    lio::ClusterCounts cc;
-    rc = lio::euclidean_clusters(f->dn, f->cl, f->d_in, n, stride, tolerance, min_size, max_size, cap_clusters, &cc, f->st);
-    if (rc) return status(rc, "lio_euclidean_clusters");
-    const int64_t m = std::min(cc.clusters, cap_clusters);
+    return upload_in(f, pts, n * stride);
+}
+
+// what both entries end with: labels, DBSCAN's core flags, the grouped indices, offsets and boxes of the first
+// min(clusters, cap_clusters) clusters, the wait, and the counts (stats[2] = clusters, stats[3] = points in them)
+static int cluster_download(lio_filter* f, int64_t n, const int64_t (&stats)[4], int32_t* labels_out, uint8_t* core_opt,
+                            int64_t* n_clusters, int64_t cap_clusters, int64_t* offsets_opt, int32_t* indices_opt,
+                            float* aabb6_opt, int64_t* stats4_opt) {
+    const int64_t m = std::min(stats[2], cap_clusters);
     HIP_TRY(hipMemcpyAsync(labels_out, f->cl.labels, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, f->st));
-    if (indices_opt && cc.clustered_points)
-        HIP_TRY(hipMemcpyAsync(indices_opt, f->cl.indices, (size_t)cc.clustered_points * sizeof(int32_t),
-                               hipMemcpyDeviceToHost, f->st));
+    if (core_opt) HIP_TRY(hipMemcpyAsync(core_opt, f->cl.rank_of, (size_t)n, hipMemcpyDeviceToHost, f->st));
+    if (indices_opt && stats[3])
+        HIP_TRY(hipMemcpyAsync(indices_opt, f->cl.indices, (size_t)stats[3] * sizeof(int32_t), hipMemcpyDeviceToHost, f->st));
     if (offsets_opt)
         HIP_TRY(hipMemcpyAsync(offsets_opt, f->cl.offsets, (size_t)(m + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, f->st));
     if (aabb6_opt && m)
         HIP_TRY(hipMemcpyAsync(aabb6_opt, f->cl.aabb, (size_t)m * 6 * sizeof(float), hipMemcpyDeviceToHost, f->st));
     HIP_TRY(hipStreamSynchronize(f->st));
-    *n_clusters = cc.clusters;
+    *n_clusters = stats[2];
     if (stats4_opt)
-        stats4_opt[0] = cc.finite, stats4_opt[1] = cc.components, stats4_opt[2] = cc.clusters,
-        stats4_opt[3] = cc.clustered_points;
+        for (int k = 0; k < 4; ++k) stats4_opt[k] = stats[k];
     return LIO_OK;
 }
 
-// ---- DBSCAN with core flags and per-cluster bounding boxes (lio_dbscan.hip) ----
+int lio_euclidean_clusters(lio_filter* f, const float* pts, int64_t n, int stride, float tolerance, int64_t min_size,
+                           int64_t max_size, int32_t* labels_out, int64_t* n_clusters, int64_t cap_clusters,
+                           int64_t* offsets_opt, int32_t* indices_opt, float* aabb6_opt, int64_t* stats4_opt) {
+    int rc = cluster_begin(f, "lio_euclidean_clusters", pts, n, stride, tolerance, min_size, labels_out, n_clusters,
+                           cap_clusters, offsets_opt, stats4_opt);
+    if (rc || n == 0) return rc;
+    lio::ClusterCounts cc;
+    rc = lio::euclidean_clusters(f->dn, f->cl, f->d_in, n, stride, tolerance, min_size, max_size, cap_clusters, &cc, f->st);
+    if (rc) return status(rc, "lio_euclidean_clusters");
+    return cluster_download(f, n, {cc.finite, cc.components, cc.clusters, cc.clustered_points}, labels_out, nullptr,
+                            n_clusters, cap_clusters, offsets_opt, indices_opt, aabb6_opt, stats4_opt);
+}
+
 int lio_dbscan(lio_filter* f, const float* pts, int64_t n, int stride, float eps, int64_t min_samples,
                int32_t* labels_out, uint8_t* core_opt, int64_t* n_clusters, int64_t cap_clusters,
                int64_t* offsets_opt, int32_t* indices_opt, float* aabb6_opt, int64_t* stats4_opt) {
-    int rc = denoise_handle(f, "lio_dbscan");
-    if (rc) return rc;
-    if (!n_clusters || n < 0 || n >= (int64_t)1 << 31 || (n > 0 && (!pts || !labels_out)) || stride < 3 ||
-        stride > lio::kMaxFields || !(eps > 0.f) || !std::isfinite(eps) || min_samples < 1 || cap_clusters < 0)
-        return fail(LIO_ERR_ARG, "lio_dbscan: bad arguments");
-    *n_clusters = 0;
-    if (stats4_opt)
-        for (int k = 0; k < 4; ++k) stats4_opt[k] = 0;
-    if (offsets_opt) offsets_opt[0] = 0;
-    if (n == 0) return LIO_OK;
-    HIP_TRY(hipSetDevice(f->dev));
-    rc = grow(&f->d_in, f->in_cap, n * stride);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(f->d_in, pts, (size_t)n * stride * sizeof(float), hipMemcpyHostToDevice, f->st));
+    int rc = cluster_begin(f, "lio_dbscan", pts, n, stride, eps, min_samples, labels_out, n_clusters, cap_clusters,
+                           offsets_opt, stats4_opt);
+    if (rc || n == 0) return rc;
     lio::DbscanCounts dc;
     rc = lio::dbscan(f->dn, f->cl, f->d_in, n, stride, eps, min_samples, cap_clusters, &dc, f->st);
     if (rc) return status(rc, "lio_dbscan");
-    const int64_t m = std::min(dc.clusters, cap_clusters);
-    HIP_TRY(hipMemcpyAsync(labels_out, f->cl.labels, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, f->st));
-    if (core_opt) HIP_TRY(hipMemcpyAsync(core_opt, f->cl.rank_of, (size_t)n, hipMemcpyDeviceToHost, f->st));
-    if (indices_opt && dc.clustered_points)
-        HIP_TRY(hipMemcpyAsync(indices_opt, f->cl.indices, (size_t)dc.clustered_points * sizeof(int32_t),
-                               hipMemcpyDeviceToHost, f->st));
-    if (offsets_opt)
-        HIP_TRY(hipMemcpyAsync(offsets_opt, f->cl.offsets, (size_t)(m + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, f->st));
-    if (aabb6_opt && m)
-        HIP_TRY(hipMemcpyAsync(aabb6_opt, f->cl.aabb, (size_t)m * 6 * sizeof(float), hipMemcpyDeviceToHost, f->st));
-    HIP_TRY(hipStreamSynchronize(f->st));
-    *n_clusters = dc.clusters;
-    if (stats4_opt)
-        stats4_opt[0] = dc.finite, stats4_opt[1] = dc.core, stats4_opt[2] = dc.clusters,
-        stats4_opt[3] = dc.clustered_points;
-    return LIO_OK;
+    return cluster_download(f, n, {dc.finite, dc.core, dc.clusters, dc.clustered_points}, labels_out, core_opt, n_clusters,
+                            cap_clusters, offsets_opt, indices_opt, aabb6_opt, stats4_opt);
 }
 
 // ---- RANSAC plane segmentation (lio_plane.hip) ----
@@ -1520,9 +1513,7 @@ int lio_segment_plane(lio_filter* f, const float* pts, int64_t n, int stride, fl
     }
     lio::plane_hypotheses(pts, stride, tri, K, pb.h_planes.data(), pb.h_deg.data());
     HIP_TRY(hipSetDevice(f->dev));
-    rc = grow(&f->d_in, f->in_cap, n * stride);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(f->d_in, pts, (size_t)n * stride * sizeof(float), hipMemcpyHostToDevice, f->st));
+    if ((rc = upload_in(f, pts, n * stride))) return rc;
     lio::PlaneResult pr;
     rc = lio::segment_plane(f->dn, pb, f->d_in, pts, n, stride, distance_threshold, K, refit4_opt != nullptr, &pr, f->st);
     if (rc) return status(rc, "lio_segment_plane");
@@ -1796,10 +1787,9 @@ int lio_cloud2_encode(lio_filter* f, const float* rec, int64_t n, int stride, co
     if (n == 0) return LIO_OK;
     HIP_TRY(hipSetDevice(f->dev));
     const int64_t bytes = n * point_step;
-    int rc = grow(&f->d_in, f->in_cap, n * stride);
-    if (!rc) rc = grow(&f->d_out, f->out_cap, (bytes + 3) / 4);
+    int rc = grow(&f->d_out, f->out_cap, (bytes + 3) / 4);
+    if (!rc) rc = upload_in(f, rec, n * stride);
     if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(f->d_in, rec, (size_t)n * stride * sizeof(float), hipMemcpyHostToDevice, f->st));
     rc = lio::cloud_encode(f->d_in, n, stride, point_step, reinterpret_cast<const lio::CloudField*>(fields), n_fields,
                            reinterpret_cast<uint8_t*>(f->d_out), f->st);
     if (rc) return status(rc, "lio_cloud2_encode");

@@ -23,6 +23,7 @@
 #include "lio_dev.hpp"
 #include "lio_scratch_cub.hpp"
 #include "lio_denoise.hpp"
+#include "lio_radius_dev.hpp"  // cell_box: Kernel B's cell range (shared with the clusterers)
 
 namespace lio {
 
@@ -342,12 +343,9 @@ __global__ void __launch_bounds__(64) sor_knn_kernel(const float4* __restrict__ 
 }
 
 // ---- kernel B ---------------------------------------------------------------------------------------
-// One thread per cloud point over the grid of the seeds: the cells from cell_coord(p - (r + m)) to
-// cell_coord(p + (r + m)) per axis.  A seed s with float sqdist3(p, s) < r2 has |p.x - s.x| <= r (1 + 3e-7)
-// (the roundings of the difference, the squares and r2), so with m = 1e-5 r + 1e-6 |p.x| the float
-// p.x - (r + m) is <= s.x, and by the monotone cell assignment the seed's cell is inside the scanned range:
-// no seed within the radius is missed, whatever the cell size.  The lowest index wins, so the result does not
-// depend on the scan order.
+// One thread per cloud point over the grid of the seeds: every row of cell_box (lio_radius_dev.hpp, with the
+// reason why it holds every seed within the radius).  The lowest index wins, so the result does not depend on
+// the scan order.
 __global__ void radius_seed_kernel(const float* __restrict__ p, int64_t n, int stride, const float4* __restrict__ seeds,
                                    const uint32_t* __restrict__ start, const DnGeom* __restrict__ geom, float r, float r2,
                                    int32_t* __restrict__ seed_out, float* __restrict__ d2_out) {
@@ -359,23 +357,18 @@ __global__ void radius_seed_kernel(const float* __restrict__ p, int64_t n, int s
     int best = 0x7fffffff;
     float bd = 0.f;
     if (isfinite(x) && isfinite(y) && isfinite(z)) {
-        const float rx = r + (1e-5f * r + 1e-6f * fabsf(x)), ry = r + (1e-5f * r + 1e-6f * fabsf(y)),
-                    rz = r + (1e-5f * r + 1e-6f * fabsf(z));
-        const int x0 = max(cell_coord(x - rx, g.ox, g.inv), 0), x1 = min(cell_coord(x + rx, g.ox, g.inv), g.nx - 1);
-        const int y0 = max(cell_coord(y - ry, g.oy, g.inv), 0), y1 = min(cell_coord(y + ry, g.oy, g.inv), g.ny - 1);
-        const int z0 = max(cell_coord(z - rz, g.oz, g.inv), 0), z1 = min(cell_coord(z + rz, g.oz, g.inv), g.nz - 1);
-        if (x0 <= x1)
-            for (int cz = z0; cz <= z1; ++cz)
-                for (int cy = y0; cy <= y1; ++cy) {
-                    const uint32_t base = ((uint32_t)cz * (uint32_t)g.ny + (uint32_t)cy) * (uint32_t)g.nx;
-                    const uint32_t e = start[base + (uint32_t)x1 + 1u];
-                    for (uint32_t k = start[base + (uint32_t)x0]; k < e; ++k) {
-                        const float4 s = seeds[k];
-                        const float d = sqdist3(x, y, z, s.x, s.y, s.z);
-                        const int id = __float_as_int(s.w);
-                        if (d < r2 && id < best) best = id, bd = d;  // FLANN's radius set keeps dist < radius [U]
-                    }
+        const auto b = cell_box<false>(g, x, y, z, r);
+        for (int cz = b.z0; cz <= b.z1; ++cz)
+            for (int cy = b.y0; cy <= b.y_last(cz); ++cy) {
+                uint32_t k, e;
+                b.row(g, start, cz, cy, k, e);
+                for (; k < e; ++k) {
+                    const float4 s = seeds[k];
+                    const float d = sqdist3(x, y, z, s.x, s.y, s.z);
+                    const int id = __float_as_int(s.w);
+                    if (d < r2 && id < best) best = id, bd = d;  // FLANN's radius set keeps dist < radius [U]
                 }
+            }
     }
     seed_out[i] = best == 0x7fffffff ? -1 : best;
     if (d2_out) d2_out[i] = bd;

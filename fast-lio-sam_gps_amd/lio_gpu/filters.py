@@ -143,6 +143,30 @@ def denoise_slam_map(pts, seed_thres=2800.0, cluster_seed_radius=1.0, denoise_ra
     return out[: m.value].copy(), counts
 
 
+def _cluster_call(entry, handle, pts, params, cap_clusters, with_core):
+    """Allocates the outputs of ``lio_euclidean_clusters`` / ``lio_dbscan`` (``entry``; ``params`` are its arguments
+    between the stride and ``labels_out``), calls it and slices the result: the cluster count, labels, core flags
+    (``None`` without ``with_core``), offsets, indices, boxes, stats and the list of index arrays."""
+    pts2 = _rows(pts)
+    n = len(pts2)
+    cap = n if cap_clusters is None else int(cap_clusters)
+    labels = np.full(n, -1, np.int32)
+    core = np.zeros(n, np.uint8) if with_core else None
+    offsets = np.zeros(max(cap, 0) + 1, np.int64)
+    indices = np.zeros(n, np.int32)
+    aabb = np.zeros((max(cap, 0), 6), np.float32)
+    stats = np.zeros(4, np.int64)
+    m = C.c_int64(0)
+    i32p, i64p = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+    core_arg = (core.ctypes.data_as(C.POINTER(C.c_uint8)),) if with_core else ()
+    check(entry(handle, _fp(pts2), n, pts2.shape[1], *params, labels.ctypes.data_as(i32p), *core_arg, C.byref(m), cap,
+                offsets.ctypes.data_as(i64p), indices.ctypes.data_as(i32p), _fp(aabb), stats.ctypes.data_as(i64p)))
+    k = min(m.value, cap)
+    offsets, indices = offsets[: k + 1].copy(), indices[: stats[3]].copy()
+    return (m.value, labels, core, offsets, indices, aabb[:k].copy(), stats,
+            [indices[offsets[t]:offsets[t + 1]] for t in range(k)])
+
+
 class EuclideanClusterExtraction(_Handle):
     """``pcl::EuclideanClusterExtraction``: the connected components of the graph that joins two finite points
     closer than ``tolerance`` (strict, float squared distances), those with ``min_size <= size <= max_size``
@@ -179,26 +203,9 @@ class EuclideanClusterExtraction(_Handle):
         """The list of index arrays.  ``cap_clusters`` (default: as many as there can be) bounds the clusters
         that ``offsets`` / ``aabb`` and the returned list describe; ``labels``, ``indices`` and ``stats`` are
         always complete."""
-        pts2 = _rows(pts)
-        n = len(pts2)
-        cap = n if cap_clusters is None else int(cap_clusters)
-        labels = np.full(n, -1, np.int32)
-        offsets = np.zeros(max(cap, 0) + 1, np.int64)
-        indices = np.zeros(n, np.int32)
-        aabb = np.zeros((max(cap, 0), 6), np.float32)
-        stats = np.zeros(4, np.int64)
-        m = C.c_int64(0)
-        i32p, i64p = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
-        check(lib().lio_euclidean_clusters(self._h, _fp(pts2), n, pts2.shape[1], self.tolerance, self.min_size,
-                                           self.max_size, labels.ctypes.data_as(i32p), C.byref(m), cap,
-                                           offsets.ctypes.data_as(i64p), indices.ctypes.data_as(i32p), _fp(aabb),
-                                           stats.ctypes.data_as(i64p)))
-        k = min(m.value, cap)
-        self.n_clusters = m.value
-        self.labels, self.stats = labels, stats
-        self.offsets, self.aabb = offsets[: k + 1].copy(), aabb[:k].copy()
-        self.indices = indices[: stats[3]].copy()
-        return [self.indices[self.offsets[t]:self.offsets[t + 1]] for t in range(k)]
+        (self.n_clusters, self.labels, _, self.offsets, self.indices, self.aabb, self.stats, clusters) = _cluster_call(
+            lib().lio_euclidean_clusters, self._h, pts, (self.tolerance, self.min_size, self.max_size), cap_clusters, False)
+        return clusters
 
 
 class DBSCAN(_Handle):
@@ -228,28 +235,10 @@ class DBSCAN(_Handle):
         """The list of index arrays.  ``cap_clusters`` (default: as many as there can be) bounds the clusters
         that ``offsets`` / ``aabb`` and the returned list describe; ``labels_``, ``core_sample_indices_``,
         ``indices`` and ``stats`` are always complete."""
-        pts2 = _rows(pts)
-        n = len(pts2)
-        cap = n if cap_clusters is None else int(cap_clusters)
-        labels = np.full(n, -1, np.int32)
-        core = np.zeros(n, np.uint8)
-        offsets = np.zeros(max(cap, 0) + 1, np.int64)
-        indices = np.zeros(n, np.int32)
-        aabb = np.zeros((max(cap, 0), 6), np.float32)
-        stats = np.zeros(4, np.int64)
-        m = C.c_int64(0)
-        i32p, i64p = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
-        check(lib().lio_dbscan(self._h, _fp(pts2), n, pts2.shape[1], self.eps, self.min_samples,
-                               labels.ctypes.data_as(i32p), core.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(m), cap,
-                               offsets.ctypes.data_as(i64p), indices.ctypes.data_as(i32p), _fp(aabb),
-                               stats.ctypes.data_as(i64p)))
-        k = min(m.value, cap)
-        self.n_clusters = m.value
-        self.labels_, self.stats = labels, stats
+        (self.n_clusters, self.labels_, core, self.offsets, self.indices, self.aabb, self.stats, clusters) = _cluster_call(
+            lib().lio_dbscan, self._h, pts, (self.eps, self.min_samples), cap_clusters, True)
         self.core_sample_indices_ = np.flatnonzero(core).astype(np.int64)
-        self.offsets, self.aabb = offsets[: k + 1].copy(), aabb[:k].copy()
-        self.indices = indices[: stats[3]].copy()
-        return [self.indices[self.offsets[t]:self.offsets[t + 1]] for t in range(k)]
+        return clusters
 
 
 def sample_triples(seed: int, n: int, num_iterations: int) -> np.ndarray:

@@ -609,6 +609,31 @@ struct ClusterAABB {  // float min / max of x, y, z over a cluster's members (po
     float min[3], max[3];
 };
 
+// What EuclideanClusterExtraction and DBSCAN share: the outputs of the last extract() and the call that fills them.
+struct ClusterOutputs {
+    std::vector<int32_t> labels;
+    std::vector<ClusterAABB> aabbs;
+    int64_t stats[4] = {0, 0, 0, 0};
+
+    // call(labels_out, n_clusters, cap_clusters, offsets, indices, aabb6, stats4): the entry point with its
+    // leading arguments bound
+    template <class Call>
+    void run(int64_t n, std::vector<PointIndices>& clusters, const char* what, Call call) {
+        labels.assign((size_t)n, -1);
+        std::vector<int32_t> idx((size_t)n);
+        std::vector<int64_t> off((size_t)n + 1, 0);
+        std::vector<float> box(6 * (size_t)n);
+        int64_t m = 0;
+        check(call(labels.data(), &m, n, off.data(), idx.data(), box.data(), stats), what);
+        clusters.assign((size_t)m, PointIndices{});
+        aabbs.resize((size_t)m);
+        for (int64_t k = 0; k < m; ++k) {
+            clusters[(size_t)k].indices.assign(idx.begin() + off[(size_t)k], idx.begin() + off[(size_t)k + 1]);
+            std::memcpy(&aabbs[(size_t)k], &box[6 * (size_t)k], sizeof(ClusterAABB));
+        }
+    }
+};
+
 // pcl::EuclideanClusterExtraction<PointT>: setInputCloud / setClusterTolerance / setMinClusterSize /
 // setMaxClusterSize / extract (clustering_and_denoise, fast_lio_sam.cpp:343-363).  Clusters by size descending,
 // then lowest member index (lio_gpu.h); indices ascend inside a cluster.  The defaults are PCL's: tolerance 0
@@ -624,27 +649,16 @@ public:
     void extract(std::vector<PointIndices>& clusters) {
         if (!in_) throw Error(LIO_ERR_ARG, "EuclideanClusterExtraction: no input cloud");
         const int64_t n = (int64_t)in_->size();
-        labels_.assign((size_t)n, -1);
-        std::vector<int32_t> idx((size_t)n);
-        std::vector<int64_t> off((size_t)n + 1, 0);
-        std::vector<float> box(6 * (size_t)n);
-        int64_t m = 0;
-        check(lio_euclidean_clusters(f_.handle(), reinterpret_cast<const float*>(in_->data()), n, float_stride<PointT>(),
-                                     (float)tolerance_, min_, max_, labels_.data(), &m, n, off.data(), idx.data(),
-                                     box.data(), stats_),
-              "EuclideanClusterExtraction::extract");
-        clusters.assign((size_t)m, PointIndices{});
-        aabbs_.resize((size_t)m);
-        for (int64_t k = 0; k < m; ++k) {
-            clusters[(size_t)k].indices.assign(idx.begin() + off[(size_t)k], idx.begin() + off[(size_t)k + 1]);
-            std::memcpy(&aabbs_[(size_t)k], &box[6 * (size_t)k], sizeof(ClusterAABB));
-        }
+        out_.run(n, clusters, "EuclideanClusterExtraction::extract", [&](auto... out) {
+            return lio_euclidean_clusters(f_.handle(), reinterpret_cast<const float*>(in_->data()), n,
+                                          float_stride<PointT>(), (float)tolerance_, min_, max_, out...);
+        });
     }
     // of the last extract(): per input point the rank of its cluster (-1: none); one box per cluster; finite
     // points, components, accepted clusters, points in them
-    const std::vector<int32_t>& labels() const { return labels_; }
-    const std::vector<ClusterAABB>& aabbs() const { return aabbs_; }
-    const int64_t* stats() const { return stats_; }
+    const std::vector<int32_t>& labels() const { return out_.labels; }
+    const std::vector<ClusterAABB>& aabbs() const { return out_.aabbs; }
+    const int64_t* stats() const { return out_.stats; }
 
 private:
     FilterGPU& f_;
@@ -652,9 +666,7 @@ private:
     double tolerance_ = 0.0;  // PCL's defaults
     int min_ = 1;
     int max_ = 2147483647;
-    std::vector<int32_t> labels_;
-    std::vector<ClusterAABB> aabbs_;
-    int64_t stats_[4] = {0, 0, 0, 0};
+    ClusterOutputs out_;
 };
 
 // DBSCAN as the offline pipeline calls it (post_process/clustering.py:30-36), in the shape of
@@ -672,38 +684,26 @@ public:
     void extract(std::vector<PointIndices>& clusters) {
         if (!in_) throw Error(LIO_ERR_ARG, "DBSCAN: no input cloud");
         const int64_t n = (int64_t)in_->size();
-        labels_.assign((size_t)n, -1);
         core_.assign((size_t)n, 0);
-        std::vector<int32_t> idx((size_t)n);
-        std::vector<int64_t> off((size_t)n + 1, 0);
-        std::vector<float> box(6 * (size_t)n);
-        int64_t m = 0;
-        check(lio_dbscan(f_.handle(), reinterpret_cast<const float*>(in_->data()), n, float_stride<PointT>(), (float)eps_,
-                         min_samples_, labels_.data(), core_.data(), &m, n, off.data(), idx.data(), box.data(), stats_),
-              "DBSCAN::extract");
-        clusters.assign((size_t)m, PointIndices{});
-        aabbs_.resize((size_t)m);
-        for (int64_t k = 0; k < m; ++k) {
-            clusters[(size_t)k].indices.assign(idx.begin() + off[(size_t)k], idx.begin() + off[(size_t)k + 1]);
-            std::memcpy(&aabbs_[(size_t)k], &box[6 * (size_t)k], sizeof(ClusterAABB));
-        }
+        out_.run(n, clusters, "DBSCAN::extract", [&](int32_t* labels, auto... out) {
+            return lio_dbscan(f_.handle(), reinterpret_cast<const float*>(in_->data()), n, float_stride<PointT>(),
+                              (float)eps_, min_samples_, labels, core_.data(), out...);
+        });
     }
     // of the last extract(): per input point its cluster (-1: noise) and 1 where it is a core point; one box per
     // cluster; finite points, core points, clusters, clustered points
-    const std::vector<int32_t>& labels() const { return labels_; }
+    const std::vector<int32_t>& labels() const { return out_.labels; }
     const std::vector<uint8_t>& core() const { return core_; }
-    const std::vector<ClusterAABB>& aabbs() const { return aabbs_; }
-    const int64_t* stats() const { return stats_; }
+    const std::vector<ClusterAABB>& aabbs() const { return out_.aabbs; }
+    const int64_t* stats() const { return out_.stats; }
 
 private:
     FilterGPU& f_;
     const std::vector<PointT>* in_ = nullptr;
     double eps_ = 0.5;  // scikit-learn's defaults
     int64_t min_samples_ = 5;
-    std::vector<int32_t> labels_;
     std::vector<uint8_t> core_;
-    std::vector<ClusterAABB> aabbs_;
-    int64_t stats_[4] = {0, 0, 0, 0};
+    ClusterOutputs out_;
 };
 
 // Open3D's PointCloud::SegmentPlane as the offline pipeline calls it (post_process/clustering.py:21-28), in the

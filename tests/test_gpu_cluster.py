@@ -183,6 +183,30 @@ def test_blobs(ec, n):
         assert (ec.labels[big] == -1).all() and (ec.labels >= 0).sum() == 4097 - 660 - 262
 
 
+def test_blob_boxes_in_rank_order(ec):
+    """the boxes walk `indices` in rank order (size descending), which is not the root order of the sorted runs:
+    clusters of 660 down to 10 points change inside and across the 64-position groups of the box kernel"""
+    pts = make_cloud("blobs", 4097)
+    root = components("blobs", pts, 0.5)
+    ref = check(ec, pts, root, 0.5, 1, 4097)
+    roots = np.array([c[0] for c in ref.clusters])
+    assert len(ref.clusters) == 40 and (np.diff(roots) < 0).any()  # rank order differs from root order
+    check(ec, pts, root, 0.5, 1, 4097, cap=3)
+    np.testing.assert_array_equal(ec.aabb, ref.aabb[:3])
+
+
+def test_two_point_clusters(ec):
+    """1300 clusters of two points: a cluster boundary at every second position of `indices`, in lockstep across
+    the box kernel's 1024-position chunks"""
+    rng = np.random.default_rng(1300)
+    site = 5.0 * np.stack(np.meshgrid(*[np.arange(11)] * 3, indexing="ij"), -1).reshape(-1, 3)[:1300]
+    p = np.concatenate([site, site + [0.1, 0.0, 0.0]])
+    pts = np.concatenate([p, np.ones((len(p), 1))], 1)[rng.permutation(len(p))].astype(f32)
+    ref = check(ec, pts, components("pairs", pts, 0.5), 0.5, 2, 2)
+    assert ref.stats[1] == 1300 and ref.stats[2] == 1300 and ref.stats[3] == 2600
+    assert (np.diff(ref.offsets) == 2).all()
+
+
 @pytest.mark.parametrize("n", NS)
 def test_chain(ec, n):
     """one component through every cell and every workgroup: a union that hooks once without finding the roots
