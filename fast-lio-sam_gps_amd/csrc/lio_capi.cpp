@@ -24,6 +24,7 @@
 #include "lio_denoise.hpp"
 #include "lio_cluster.hpp"
 #include "lio_dbscan.hpp"
+#include "lio_gpsalign.hpp"
 #include "lio_plane.hpp"
 #include "lio_pool.hpp"
 #include "lio_mapupd.hpp"
@@ -1075,6 +1076,7 @@ struct lio_filter {
     lio::DenoiseBuf dn;  // lio_sor_filter / lio_radius_first_seed / lio_denoise_slam_map
     lio::ClusterBuf cl;  // lio_euclidean_clusters, lio_dbscan (with dn: the grid, the sorts and the scan)
     lio::PlaneBuf pl;    // lio_segment_plane (with dn: the flags and the scan)
+    lio::GpsAlignBuf ga; // lio_gps_align, lio_similarity2d_fit, lio_georeference_xy
 };
 
 static lio::UndistortEnd undistort_end(const lio_pose* e) {
@@ -1281,6 +1283,7 @@ int lio_filter_destroy(lio_filter* f) {
     lio::denoise_free(f->dn);
     lio::cluster_free(f->cl);
     lio::plane_free(f->pl);
+    lio::gps_align_free(f->ga);
     for (void* q : {(void*)f->d_in, (void*)f->d_out, (void*)f->d_seg, (void*)f->d_T, (void*)f->d_poses})
         if (q) (void)hipFree(q);
     (void)hipStreamDestroy(f->st);
@@ -1465,6 +1468,80 @@ int lio_dbscan(lio_filter* f, const float* pts, int64_t n, int stride, float eps
     if (rc) return status(rc, "lio_dbscan");
     return cluster_download(f, n, {dc.finite, dc.core, dc.clusters, dc.clustered_points}, labels_out, core_opt, n_clusters,
                             cap_clusters, offsets_opt, indices_opt, aabb6_opt, stats4_opt);
+}
+
+// ---- GPS-to-SLAM trajectory alignment and map georeferencing (lio_gpsalign.hip) ----
+static_assert(lio::kGaLen == LIO_GPSALIGN_LEN && lio::kGaIters == LIO_GPSALIGN_ITERATIONS &&
+                  lio::kGaConverged == LIO_GPSALIGN_CONVERGED && lio::kGaMeanError == LIO_GPSALIGN_MEAN_ERROR &&
+                  lio::kGaS0 == LIO_GPSALIGN_S0 && lio::kGaCA == LIO_GPSALIGN_CA && lio::kGaCB == LIO_GPSALIGN_CB &&
+                  lio::kGaSc == LIO_GPSALIGN_SC && lio::kGaC == LIO_GPSALIGN_C && lio::kGaS == LIO_GPSALIGN_S &&
+                  lio::kGaT == LIO_GPSALIGN_T && lio::kGaCD == LIO_GPSALIGN_CD && lio::kGaRefScale == LIO_GPSALIGN_REF_SCALE &&
+                  lio::kGaRefC == LIO_GPSALIGN_REF_C && lio::kGaRefS == LIO_GPSALIGN_REF_S &&
+                  lio::kGaRefT == LIO_GPSALIGN_REF_T && lio::kGaTotScale == LIO_GPSALIGN_TOTAL_SCALE &&
+                  lio::kGaTotC == LIO_GPSALIGN_TOTAL_C && lio::kGaTotS == LIO_GPSALIGN_TOTAL_S &&
+                  lio::kGaTotT == LIO_GPSALIGN_TOTAL_T && lio::kSimLen == LIO_SIM2D_LEN && lio::kSimScale == LIO_SIM2D_SCALE &&
+                  lio::kSimC == LIO_SIM2D_C && lio::kSimS == LIO_SIM2D_S && lio::kSimT == LIO_SIM2D_T &&
+                  lio::kGaState == LIO_ERR_STATE,
+              "the result offsets of lio_gpsalign.hpp are the public ones");
+
+static bool all_finite(const double* v, int64_t count) {
+    for (int64_t i = 0; i < count; ++i)
+        if (!std::isfinite(v[i])) return false;
+    return true;
+}
+
+// the status of the two fits: kGaState carries its own text
+static int fit_status(int rc, const char* what, const char* arg_what) {
+    if (rc == lio::kGaState) return fail(LIO_ERR_STATE, std::string(what) + ": " + lio::last_error());
+    return status(rc, what, arg_what);
+}
+
+int lio_gps_align(lio_filter* f, const double* gps_xy, int64_t m, const double* slam_xy, int64_t n, int max_iterations,
+                  double tolerance, double* aligned_xy_out, int32_t* nn_out_opt, double* out) {
+    const int rc = denoise_handle(f, "lio_gps_align");
+    if (rc) return rc;
+    if (!gps_xy || !slam_xy || !aligned_xy_out || !out || n < 1 || m < 1 || n >= (int64_t)1 << 31 ||
+        m >= (int64_t)1 << 31 || max_iterations < 1)
+        return fail(LIO_ERR_ARG, "lio_gps_align: bad arguments");
+    if (!all_finite(gps_xy, 2 * m) || !all_finite(slam_xy, 2 * n))
+        return fail(LIO_ERR_ARG, "lio_gps_align: a coordinate is not finite");
+    HIP_TRY(hipSetDevice(f->dev));
+    return fit_status(lio::gps_align(f->ga, gps_xy, m, slam_xy, n, max_iterations, tolerance, aligned_xy_out, nn_out_opt,
+                                     out, f->st),
+                      "lio_gps_align", "a point set has zero variance");
+}
+
+int lio_similarity2d_fit(lio_filter* f, const double* src_xy, const double* dst_xy, int64_t n, double* out) {
+    const int rc = denoise_handle(f, "lio_similarity2d_fit");
+    if (rc) return rc;
+    if (!src_xy || !dst_xy || !out || n < 1 || n >= (int64_t)1 << 31)
+        return fail(LIO_ERR_ARG, "lio_similarity2d_fit: bad arguments");
+    if (!all_finite(src_xy, 2 * n) || !all_finite(dst_xy, 2 * n))
+        return fail(LIO_ERR_ARG, "lio_similarity2d_fit: a coordinate is not finite");
+    HIP_TRY(hipSetDevice(f->dev));
+    return fit_status(lio::similarity2d_fit(f->ga, src_xy, dst_xy, n, out, f->st), "lio_similarity2d_fit", "bad arguments");
+}
+
+int lio_georeference_xy(lio_filter* f, const float* pts, int64_t n, int stride, double scale, const double* R4,
+                        const double* t2, const double* origin2_opt, float* out, double* xy_out_opt) {
+    int rc = denoise_handle(f, "lio_georeference_xy");
+    if (rc) return rc;
+    if (!R4 || !t2 || n < 0 || n >= (int64_t)1 << 31 || (n > 0 && (!pts || !out)) || stride < 3 || stride > lio::kMaxFields)
+        return fail(LIO_ERR_ARG, "lio_georeference_xy: bad arguments");
+    if (n == 0) return LIO_OK;
+    HIP_TRY(hipSetDevice(f->dev));
+    if ((rc = upload_in(f, pts, n * stride))) return rc;
+    if ((rc = grow(&f->d_out, f->out_cap, n * stride))) return rc;
+    if (xy_out_opt && (rc = grow(&f->ga.geo_xy, f->ga.geo_cap, n, 2))) return rc;
+    const double p[9] = {R4[0], R4[1], R4[2], R4[3], scale, t2[0], t2[1], origin2_opt ? origin2_opt[0] : 0.0,
+                         origin2_opt ? origin2_opt[1] : 0.0};
+    rc = lio::georeference_xy(f->d_in, n, stride, p, f->d_out, xy_out_opt ? f->ga.geo_xy : nullptr, f->st);
+    if (rc) return status(rc, "lio_georeference_xy");
+    HIP_TRY(hipMemcpyAsync(out, f->d_out, (size_t)n * stride * sizeof(float), hipMemcpyDeviceToHost, f->st));
+    if (xy_out_opt)
+        HIP_TRY(hipMemcpyAsync(xy_out_opt, f->ga.geo_xy, (size_t)n * 2 * sizeof(double), hipMemcpyDeviceToHost, f->st));
+    HIP_TRY(hipStreamSynchronize(f->st));
+    return LIO_OK;
 }
 
 // ---- RANSAC plane segmentation (lio_plane.hip) ----

@@ -22,6 +22,13 @@ LIO_ERR_STATE = -4
 LIO_ERR_NOMEM = -5
 LIO_SUMS_LEN = 32
 SUMS_HTH, SUMS_HTh, SUMS_NEFF, SUMS_RES, SUMS_HH = 0, 21, 27, 28, 29
+# lio_gps_align's result array (LIO_GPSALIGN_*) and lio_similarity2d_fit's (scale, c, s, tx, ty)
+LIO_GPSALIGN_LEN = 25
+(GPSALIGN_ITERATIONS, GPSALIGN_CONVERGED, GPSALIGN_MEAN_ERROR, GPSALIGN_S0, GPSALIGN_CA, GPSALIGN_CB, GPSALIGN_SC,
+ GPSALIGN_C, GPSALIGN_S, GPSALIGN_T, GPSALIGN_CD, GPSALIGN_REF_SCALE, GPSALIGN_REF_C, GPSALIGN_REF_S, GPSALIGN_REF_T,
+ GPSALIGN_TOTAL_SCALE, GPSALIGN_TOTAL_C, GPSALIGN_TOTAL_S, GPSALIGN_TOTAL_T) = (
+    0, 1, 2, 3, 4, 6, 8, 9, 10, 11, 13, 15, 16, 17, 18, 20, 21, 22, 23)
+LIO_SIM2D_LEN = 5
 
 # Every symbol include/lio_gpu.h declares (checked by tests/test_capi_symbols.py).
 EXPORTS = [
@@ -48,6 +55,7 @@ EXPORTS = [
     "lio_seq_shard_offsets", "lio_seq_shard_merge",
     "lio_sor_filter", "lio_radius_first_seed", "lio_denoise_slam_map", "lio_euclidean_clusters",
     "lio_segment_plane", "lio_plane_sample_triples", "lio_dbscan",
+    "lio_gps_align", "lio_similarity2d_fit", "lio_georeference_xy",
 ]
 
 
@@ -222,6 +230,9 @@ def _declare(L):
                                         C.POINTER(C.c_int64), C.POINTER(C.c_uint8), C.POINTER(C.c_int64),
                                         C.POINTER(C.c_uint64), C.POINTER(C.c_uint8), dp]),
         "lio_plane_sample_triples": (C.c_int, [C.c_uint64, C.c_int64, C.c_int64, C.POINTER(C.c_int32)]),
+        "lio_gps_align": (C.c_int, [vp, dp, C.c_int64, dp, C.c_int64, C.c_int, C.c_double, dp, C.POINTER(C.c_int32), dp]),
+        "lio_similarity2d_fit": (C.c_int, [vp, dp, dp, C.c_int64, dp]),
+        "lio_georeference_xy": (C.c_int, [vp, fp, C.c_int64, C.c_int, C.c_double, dp, dp, dp, fp, dp]),
         "lio_ctx_create": (C.c_int, [vp, C.POINTER(MatchParams), C.POINTER(vp)]),
         "lio_ctx_destroy": (C.c_int, [vp]),
         "lio_scan_set": (C.c_int, [vp, fp, C.c_int64]),

@@ -628,6 +628,93 @@ int lio_segment_plane(lio_filter* f, const float* pts, int64_t n, int stride, fl
  * n >= 2^31, num_iterations < 0 or > 2^20, NULL out with something to write.                                   */
 int lio_plane_sample_triples(uint64_t seed, int64_t n, int64_t num_iterations, int32_t* out);
 
+/* ------------------------------- GPS-to-SLAM trajectory alignment and map georeferencing (offline GPS leg) */
+/* Layout of lio_gps_align's result (doubles).  Pairs are (x, y); a rotation is (c, s) for [[c, -s], [s, c]]. */
+#define LIO_GPSALIGN_ITERATIONS 0  /* iterations run                                                          */
+#define LIO_GPSALIGN_CONVERGED 1   /* 1 when |prev - mean_error| < tolerance stopped the loop                 */
+#define LIO_GPSALIGN_MEAN_ERROR 2  /* the last mean_error                                                     */
+#define LIO_GPSALIGN_S0 3          /* the initial scale                                                       */
+#define LIO_GPSALIGN_CA 4          /* centroid of slam_xy (2)                                                 */
+#define LIO_GPSALIGN_CB 6          /* centroid of gps_xy (2)                                                  */
+#define LIO_GPSALIGN_SC 8          /* the last iteration's increment: scale,                                  */
+#define LIO_GPSALIGN_C 9           /*   rotation c,                                                           */
+#define LIO_GPSALIGN_S 10          /*   rotation s,                                                           */
+#define LIO_GPSALIGN_T 11          /*   translation (2),                                                      */
+#define LIO_GPSALIGN_CD 13         /*   centroid of the matched targets (2)                                   */
+#define LIO_GPSALIGN_REF_SCALE 15  /* THE REFERENCE'S RETURN TRIPLE: scale,                                   */
+#define LIO_GPSALIGN_REF_C 16      /*   rotation c,                                                           */
+#define LIO_GPSALIGN_REF_S 17      /*   rotation s,                                                           */
+#define LIO_GPSALIGN_REF_T 18      /*   translation (2)                                                       */
+#define LIO_GPSALIGN_TOTAL_SCALE 20 /* the TOTAL similarity slam_xy -> GPS frame: scale,                      */
+#define LIO_GPSALIGN_TOTAL_C 21    /*   rotation c,                                                           */
+#define LIO_GPSALIGN_TOTAL_S 22    /*   rotation s,                                                           */
+#define LIO_GPSALIGN_TOTAL_T 23    /*   translation (2)                                                       */
+#define LIO_GPSALIGN_LEN 25
+/* Layout of lio_similarity2d_fit's result (doubles): scale, rotation c, s, translation (2). */
+#define LIO_SIM2D_SCALE 0
+#define LIO_SIM2D_C 1
+#define LIO_SIM2D_S 2
+#define LIO_SIM2D_T 3
+#define LIO_SIM2D_LEN 5
+
+/* icp_alignment of the reference's offline GPS leg (post_process/align_slam_gps_icp.py:81-156): a 2-D similarity,
+ * with scale, between the SLAM trajectory (the source, slam_xy: n x 2 doubles) and the projected GPS track (the
+ * target, gps_xy: m x 2 doubles; the projection from WGS84 is the caller's) by point-to-point ICP.  This is the
+ * library's own restatement, exact to the bit: every operation is an IEEE double + - x / sqrt in the written
+ * order, no multiply-add is fused on host or device, and every sum is TREE.
+ *   TREE(v)   the only summation: v in blocks of 256 consecutive elements, the last padded with +0.0; inside a
+ *             block a[i] = a[i] + a[i + w] for i < w, for w = 128, 64, ..., 1; THE BLOCK SUMS ARE ADDED IN
+ *             ASCENDING BLOCK ORDER into a scalar that starts at 0.0 (the TREE order: this library's contract).
+ *   start     cA = (TREE(Ax) / n, TREE(Ay) / n) over the source A, cB likewise over the target B (/ m);
+ *             Ac = A - cA, Bc = B - cB; sA = sqrt(TREE(Acx Acx + Acy Acy)), sB likewise; s0 = sB / sA if
+ *             sA > 1e-8, else 1; S = s0 Ac, D = Bc.
+ *   iteration i = 0 .. max_iterations - 1:
+ *     1 nearest neighbour: source j takes the target k with the smallest d2 = (dx dx) + (dy dy), dx = Sx[j] -
+ *       Dx[k], dy = Sy[j] - Dy[k]; AN EQUAL d2 GOES TO THE LOWEST INDEX k; dist[j] = sqrt(d2).  The comparison is
+ *       on d2, not on the rooted distance as in numpy: the two differ only where two distinct d2 round to one
+ *       square root (this library's contract).
+ *     2 cs = (TREE(Sx) / n, TREE(Sy) / n); cd = (TREE(Mx) / n, TREE(My) / n) over the matched targets M[j] = D[k_j].
+ *     3 with a = S - cs, b = M - cd: h00 = TREE(ax bx), h01 = TREE(ax by), h10 = TREE(ay bx), h11 = TREE(ay by),
+ *       saa = TREE(ax ax + ay ay), sbb = TREE(bx bx + by by).
+ *     4 p = h00 + h11, q = h01 - h10, r = sqrt(p p + q q); (c, s) = (p / r, q / r), or (1, 0) when r == 0: the
+ *       proper rotation that maximises tr(R H), which in 2-D is the reference's SVD with its determinant fix.
+ *     5 sc = sqrt(sbb) / sqrt(saa) (the reference's norm ratio, not the least-squares scale);
+ *       t = cd - sc (R cs) with R v = (c vx - s vy, s vx + c vy).
+ *     6 S <- (sc (c Sx - s Sy) + tx, sc (s Sx + c Sy) + ty).
+ *     7 mean_error = TREE(dist) / n (the distances from before step 6, as in the reference); stop with converged = 1
+ *       if |prev - mean_error| < tolerance, else prev = mean_error; prev starts at +inf.
+ * aligned_xy_out (n x 2): the final S, in the centred frame — add cB for the GPS frame.  nn_out_opt (n, may be
+ * NULL): the last iteration's indices k_j.  out: LIO_GPSALIGN_LEN doubles, offsets above.
+ *   reference return  THE REFERENCE'S RETURN TRIPLE, by its own closing formula (align_slam_gps_icp.py:152-154):
+ *             scale = s0 sc, R = (c, s), T = cB + sc (R v), v = cd - s0 (R^T u), u = cB - t, R^T u = (c ux + s uy,
+ *             c uy - s ux) — of the LAST iteration only.  It chains the last increment with the initial scale, not
+ *             the accumulated transform: a quirk of the reference, reproduced under that name (the reference-return
+ *             quirk) for callers that compare with the script.
+ *   total     the similarity that maps slam_xy to the aligned points in the GPS frame, composed on the host: start
+ *             (S, C, Sn) = (s0, 1, 0), T = -(s0 cA); per iteration S <- sc S, (C, Sn) <- (c C - s Sn, s C + c Sn),
+ *             T <- sc (R T) + t; at the end T <- T + cB.  This is what georeferencing wants.
+ * LIO_ERR_ARG before any device work: a NULL pointer (nn_out_opt excepted), n < 1, m < 1, n or m >= 2^31,
+ * max_iterations < 1, a non-finite coordinate (a host scan); after the start: sA or sB is 0 (the reference raises on
+ * "zero variance").  LIO_ERR_STATE: saa == 0 or sc not finite in an iteration.  Repeated calls give identical bits. */
+int lio_gps_align(lio_filter* f, const double* gps_xy, int64_t m, const double* slam_xy, int64_t n, int max_iterations,
+                  double tolerance, double* aligned_xy_out, int32_t* nn_out_opt, double* out);
+/* align_trajectories_horn (georef_mapmatch.py:115-135; the timestamp-matched scripts): steps 2-5 of one iteration
+ * of lio_gps_align on the n given pairs, M = dst_xy paired one to one with S = src_xy, in the same TREE order.
+ * out: LIO_SIM2D_LEN doubles: dst ~ scale R src + t.  LIO_ERR_ARG: a NULL pointer, n < 1 or >= 2^31, a non-finite
+ * coordinate.  LIO_ERR_STATE: saa == 0 (one pair, or all sources equal) or a scale that is not finite.           */
+int lio_similarity2d_fit(lio_filter* f, const double* src_xy, const double* dst_xy, int64_t n, double* out);
+/* The map transform of post_process/georeference_pcd.py:236-244 on point records (n x stride floats, x, y, z
+ * first; stride 3..8; 0 <= n < 2^31).  Per point, in double from the float32 x, y, in this order:
+ *   gx = ((x r00) + (y r01)) scale + tx - ox,  gy = ((x r10) + (y r11)) scale + ty - oy
+ * with R4 = r00, r01, r10, r11, t2 = tx, ty and origin2_opt = ox, oy (NULL: 0, 0, the reference's behaviour).
+ * out (n x stride): the records with x, y replaced by (float)gx, (float)gy, every other field bit-copied.
+ * xy_out_opt (n x 2 doubles, may be NULL): gx, gy at full precision.  At national-grid magnitudes (HK1980:
+ * about 8e5 m) a float32 x, y quantises to 6 cm; a non-zero origin near the map keeps the float32 records
+ * fine-grained, and is the reason the parameter exists.  LIO_ERR_ARG: NULL R4 / t2, NULL pts or out with n > 0,
+ * stride outside 3..8, n < 0 or >= 2^31.                                                                        */
+int lio_georeference_xy(lio_filter* f, const float* pts, int64_t n, int stride, double scale, const double* R4,
+                        const double* t2, const double* origin2_opt, float* out, double* xy_out_opt);
+
 /* ------------------------------------------- wire / disk formats (§8(f) row 4) */
 /* One output column of a packed point record: byte offset, sensor_msgs/PointField datatype
  * (INT8 1, UINT8 2, INT16 3, UINT16 4, INT32 5, UINT32 6, FLOAT32 7, FLOAT64 8; 0 = absent -> 0)

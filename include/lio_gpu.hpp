@@ -706,6 +706,85 @@ private:
     ClusterOutputs out_;
 };
 
+// A 2-D similarity dst = scale * R * src + t, R = [[c, -s], [s, c]].
+struct Similarity2D {
+    double scale = 1.0, c = 1.0, s = 0.0, t[2] = {0.0, 0.0};
+    void apply(const double src[2], double dst[2]) const {
+        const double x = src[0], y = src[1];
+        dst[0] = scale * (c * x - s * y) + t[0];
+        dst[1] = scale * (s * x + c * y) + t[1];
+    }
+};
+
+// icp_alignment of the offline GPS leg (post_process/align_slam_gps_icp.py:81-156), in the shape of DBSCAN:
+// setMaxIterations / setTolerance / align.  Coordinates are (x, y) pairs of doubles, already projected.  Nearest
+// neighbours by squared distance with the lowest index on a tie, sums in the TREE order, the rotation in closed
+// form (lio_gpu.h, lio_gps_align).  total() maps the input SLAM points to the GPS frame; referenceReturn() is what
+// the reference's function returns, which chains only the last iteration's increment (a quirk of the script).
+// The defaults are the reference's: 50 iterations, tolerance 1e-4.
+class GpsAligner {
+public:
+    explicit GpsAligner(FilterGPU& f) : f_(f) {}
+    void setMaxIterations(int iterations) { iters_ = iterations; }
+    void setTolerance(double tolerance) { tol_ = tolerance; }
+    // aligned: the SLAM points in the GPS frame (n x 2)
+    void align(const std::vector<double>& gps_xy, const std::vector<double>& slam_xy, std::vector<double>& aligned) {
+        if (gps_xy.size() % 2 || slam_xy.size() % 2) throw Error(LIO_ERR_ARG, "GpsAligner: (x, y) pairs expected");
+        const int64_t m = (int64_t)gps_xy.size() / 2, n = (int64_t)slam_xy.size() / 2;
+        aligned.assign(slam_xy.size(), 0.0);
+        nn_.assign((size_t)n, 0);
+        check(lio_gps_align(f_.handle(), gps_xy.data(), m, slam_xy.data(), n, iters_, tol_, aligned.data(), nn_.data(),
+                            out_),
+              "GpsAligner::align");
+        for (int64_t j = 0; j < n; ++j)
+            for (int d = 0; d < 2; ++d) aligned[(size_t)(2 * j + d)] += out_[LIO_GPSALIGN_CB + d];
+    }
+    // of the last align()
+    int iterations() const { return (int)out_[LIO_GPSALIGN_ITERATIONS]; }
+    bool converged() const { return out_[LIO_GPSALIGN_CONVERGED] != 0.0; }
+    double meanError() const { return out_[LIO_GPSALIGN_MEAN_ERROR]; }
+    const std::vector<int32_t>& nearest() const { return nn_; }
+    Similarity2D total() const {
+        return {out_[LIO_GPSALIGN_TOTAL_SCALE], out_[LIO_GPSALIGN_TOTAL_C], out_[LIO_GPSALIGN_TOTAL_S],
+                {out_[LIO_GPSALIGN_TOTAL_T], out_[LIO_GPSALIGN_TOTAL_T + 1]}};
+    }
+    Similarity2D referenceReturn() const {
+        return {out_[LIO_GPSALIGN_REF_SCALE], out_[LIO_GPSALIGN_REF_C], out_[LIO_GPSALIGN_REF_S],
+                {out_[LIO_GPSALIGN_REF_T], out_[LIO_GPSALIGN_REF_T + 1]}};
+    }
+    const double* raw() const { return out_; }
+
+private:
+    FilterGPU& f_;
+    int iters_ = 50;
+    double tol_ = 1e-4;
+    std::vector<int32_t> nn_;
+    double out_[LIO_GPSALIGN_LEN] = {};
+};
+
+// align_trajectories_horn (georef_mapmatch.py:115-135) on pairs matched one to one: dst ~ scale * R * src + t
+inline Similarity2D fit_pairs(FilterGPU& f, const std::vector<double>& src_xy, const std::vector<double>& dst_xy) {
+    if (src_xy.size() != dst_xy.size() || src_xy.size() % 2) throw Error(LIO_ERR_ARG, "fit_pairs: equal numbers of (x, y) pairs expected");
+    double o[LIO_SIM2D_LEN];
+    check(lio_similarity2d_fit(f.handle(), src_xy.data(), dst_xy.data(), (int64_t)src_xy.size() / 2, o), "fit_pairs");
+    return {o[LIO_SIM2D_SCALE], o[LIO_SIM2D_C], o[LIO_SIM2D_S], {o[LIO_SIM2D_T], o[LIO_SIM2D_T + 1]}};
+}
+
+// the map transform of post_process/georeference_pcd.py:236-244: x, y of every record through the similarity, in
+// double, minus `origin` (0, 0: the reference; float32 x, y at national-grid magnitudes quantise to centimetres, a
+// non-zero origin near the map avoids it); every other field copied.  xy_opt: the n x 2 doubles at full precision.
+template <typename PointT>
+void georeference(FilterGPU& f, const std::vector<PointT>& in, const Similarity2D& T, std::vector<PointT>& out,
+                  const double origin[2] = nullptr, std::vector<double>* xy_opt = nullptr) {
+    const int64_t n = (int64_t)in.size();
+    out.resize(in.size());
+    if (xy_opt) xy_opt->assign(2 * in.size(), 0.0);
+    const double R4[4] = {T.c, -T.s, T.s, T.c};
+    check(lio_georeference_xy(f.handle(), reinterpret_cast<const float*>(in.data()), n, float_stride<PointT>(), T.scale,
+                              R4, T.t, origin, reinterpret_cast<float*>(out.data()), xy_opt ? xy_opt->data() : nullptr),
+          "georeference");
+}
+
 // Open3D's PointCloud::SegmentPlane as the offline pipeline calls it (post_process/clustering.py:21-28), in the
 // shape of pcl::SACSegmentation: setInputCloud / setDistanceThreshold / setMaxIterations / setSeed / segment.
 // Every hypothesis is evaluated; the winner minimises (-inliers, fixed-point squared error, hypothesis index)
