@@ -24,6 +24,7 @@
 #include "lio_denoise.hpp"
 #include "lio_cluster.hpp"
 #include "lio_dbscan.hpp"
+#include "lio_colorize.hpp"
 #include "lio_gpsalign.hpp"
 #include "lio_plane.hpp"
 #include "lio_pool.hpp"
@@ -227,6 +228,14 @@ int lio_abi_struct_sizes(int64_t* out, int n) {
                           (int64_t)sizeof(lio_imu_pose),     (int64_t)sizeof(lio_scan_prep_params),
                           (int64_t)sizeof(lio_cloud_field),  (int64_t)sizeof(lio_kernel_timing),
                           (int64_t)sizeof(lio_denoise_params)};
+    constexpr int kN = (int)(sizeof(sz) / sizeof(sz[0]));
+    if (out)
+        for (int i = 0; i < n && i < kN; ++i) out[i] = sz[i];
+    return kN;
+}
+
+int lio_abi_camera_struct_sizes(int64_t* out, int n) {
+    const int64_t sz[] = {(int64_t)sizeof(lio_camera), (int64_t)sizeof(lio_colorize_params)};
     constexpr int kN = (int)(sizeof(sz) / sizeof(sz[0]));
     if (out)
         for (int i = 0; i < n && i < kN; ++i) out[i] = sz[i];
@@ -1077,6 +1086,7 @@ struct lio_filter {
     lio::ClusterBuf cl;  // lio_euclidean_clusters, lio_dbscan (with dn: the grid, the sorts and the scan)
     lio::PlaneBuf pl;    // lio_segment_plane (with dn: the flags and the scan)
     lio::GpsAlignBuf ga; // lio_gps_align, lio_similarity2d_fit, lio_georeference_xy
+    lio::ProjectBuf pj;  // lio_project_points
 };
 
 static lio::UndistortEnd undistort_end(const lio_pose* e) {
@@ -1284,6 +1294,7 @@ int lio_filter_destroy(lio_filter* f) {
     lio::cluster_free(f->cl);
     lio::plane_free(f->pl);
     lio::gps_align_free(f->ga);
+    lio::project_free(f->pj);
     for (void* q : {(void*)f->d_in, (void*)f->d_out, (void*)f->d_seg, (void*)f->d_T, (void*)f->d_poses})
         if (q) (void)hipFree(q);
     (void)hipStreamDestroy(f->st);
@@ -1541,6 +1552,170 @@ int lio_georeference_xy(lio_filter* f, const float* pts, int64_t n, int stride, 
     if (xy_out_opt)
         HIP_TRY(hipMemcpyAsync(xy_out_opt, f->ga.geo_xy, (size_t)n * 2 * sizeof(double), hipMemcpyDeviceToHost, f->st));
     HIP_TRY(hipStreamSynchronize(f->st));
+    return LIO_OK;
+}
+
+// ---- camera projection and point cloud colorization (lio_colorize.hip) ----
+// The camera and pose checks shared by lio_project_points and lio_colorizer_add_frame: every failure names its bound.
+static int camera_arg(const std::string& what, const lio_camera* cam, const double* Rt, lio::CamArg* a) {
+    if (!cam) return fail(LIO_ERR_ARG, what + ": cam is NULL");
+    if (!Rt) return fail(LIO_ERR_ARG, what + ": Rt is NULL");
+    if (cam->width < 1 || cam->height < 1) return fail(LIO_ERR_ARG, what + ": width and height must be at least 1");
+    if ((int64_t)cam->width * (int64_t)cam->height >= (int64_t)1 << 31)
+        return fail(LIO_ERR_ARG, what + ": width x height must be below 2^31");
+    const double k[4] = {cam->fx, cam->fy, cam->cx, cam->cy};
+    if (!all_finite(k, 4)) return fail(LIO_ERR_ARG, what + ": an intrinsic (fx, fy, cx, cy) is not finite");
+    if (!all_finite(cam->dist, 8)) return fail(LIO_ERR_ARG, what + ": a distortion coefficient is not finite");
+    if (!all_finite(Rt, 12)) return fail(LIO_ERR_ARG, what + ": a pose entry of Rt is not finite");
+    if (!(cam->r2_max >= 0.0)) return fail(LIO_ERR_ARG, what + ": r2_max must be >= 0 (+inf: no limit) and not NaN");
+    a->fx = cam->fx, a->fy = cam->fy, a->cx = cam->cx, a->cy = cam->cy;
+    a->k1 = cam->dist[0], a->k2 = cam->dist[1], a->p1 = cam->dist[2], a->p2 = cam->dist[3];
+    a->k3 = cam->dist[4], a->k4 = cam->dist[5], a->k5 = cam->dist[6], a->k6 = cam->dist[7];
+    a->r2_max = cam->r2_max;
+    for (int i = 0; i < 9; ++i) a->R[i] = Rt[i];
+    for (int i = 0; i < 3; ++i) a->t[i] = Rt[9 + i];
+    a->width = cam->width, a->height = cam->height;
+    return LIO_OK;
+}
+
+static int cloud_arg(const std::string& what, const float* pts, int64_t n, int stride) {
+    if (n < 0 || n >= (int64_t)1 << 31) return fail(LIO_ERR_ARG, what + ": n must be in 0 .. 2^31 - 1");
+    if (stride < 3 || stride > lio::kMaxFields) return fail(LIO_ERR_ARG, what + ": stride must be in 3..8");
+    if (!pts && n > 0) return fail(LIO_ERR_ARG, what + ": pts is NULL");
+    return LIO_OK;
+}
+
+int lio_project_points(lio_filter* f, const float* pts, int64_t n, int stride, const lio_camera* cam, const double* Rt,
+                       double* uv_opt, double* zc_opt, int32_t* pix_opt, uint8_t* valid) {
+    const char* what = "lio_project_points";
+    int rc = denoise_handle(f, what);
+    if (rc) return rc;
+    if ((rc = cloud_arg(what, pts, n, stride))) return rc;
+    lio::CamArg a{};
+    if ((rc = camera_arg(what, cam, Rt, &a))) return rc;
+    if (!valid) return fail(LIO_ERR_ARG, std::string(what) + ": valid is NULL");
+    if (n == 0) return LIO_OK;
+    HIP_TRY(hipSetDevice(f->dev));
+    if ((rc = upload_in(f, pts, n * stride))) return rc;
+    return status(lio::project_points(f->pj, f->d_in, n, stride, a, uv_opt, zc_opt, pix_opt, valid, f->st), what);
+}
+
+static const lio_colorize_params kColorizeDefaults = {0, 0, 0.f, 0.f, 1};
+
+static int colorize_params_arg(const char* what, const lio_colorize_params* p) {
+    if (p->splat_radius < 0 || p->splat_radius > lio::kCzMaxSplat)
+        return fail(LIO_ERR_ARG, std::string(what) + ": splat_radius must be in 0..8");
+    if (!(p->depth_rel >= 0.f) || !std::isfinite(p->depth_rel) || !(p->depth_abs >= 0.f) || !std::isfinite(p->depth_abs))
+        return fail(LIO_ERR_ARG, std::string(what) + ": depth_rel and depth_abs must be finite and >= 0");
+    return LIO_OK;
+}
+
+struct lio_colorizer {
+    int dev = 0;
+    hipStream_t st = nullptr;
+    lio_colorize_params p = kColorizeDefaults;
+    lio::ColorizeBuf c;
+};
+
+int lio_colorizer_create(int device, const lio_colorize_params* params, lio_colorizer** out) {
+    if (!out) return fail(LIO_ERR_ARG, "lio_colorizer_create: out is NULL");
+    *out = nullptr;
+    int rc = check_device(device);
+    if (rc) return rc;
+    if (params && (rc = colorize_params_arg("lio_colorizer_create", params))) return rc;
+    HIP_TRY(hipSetDevice(device));
+    auto* h = new lio_colorizer();
+    h->dev = device;
+    if (params) h->p = *params;
+    if (hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking) != hipSuccess) {
+        delete h;
+        return fail(LIO_ERR_HIP, "hipStreamCreate failed");
+    }
+    if ((rc = lio::colorizer_init(h->c))) {
+        lio::colorizer_free(h->c);
+        (void)hipStreamDestroy(h->st);
+        delete h;
+        return status(rc, "lio_colorizer_create");
+    }
+    *out = h;
+    return LIO_OK;
+}
+
+int lio_colorizer_destroy(lio_colorizer* h) {
+    if (!h) return LIO_OK;
+    (void)hipSetDevice(h->dev);
+    (void)hipStreamSynchronize(h->st);
+    lio::colorizer_free(h->c);
+    (void)hipStreamDestroy(h->st);
+    delete h;
+    return LIO_OK;
+}
+
+// a NULL handle without a device is the missing device (lio_colorizer_create cannot have succeeded)
+static int colorizer_handle(lio_colorizer* h, const char* what) {
+    if (h) return LIO_OK;
+    const int rc = check_device(0);
+    if (rc) return rc;
+    return fail(LIO_ERR_ARG, std::string(what) + ": handle is NULL");
+}
+
+int lio_colorizer_set_params(lio_colorizer* h, const lio_colorize_params* params) {
+    int rc = colorizer_handle(h, "lio_colorizer_set_params");
+    if (rc) return rc;
+    if (!params) return fail(LIO_ERR_ARG, "lio_colorizer_set_params: params is NULL");
+    if ((rc = colorize_params_arg("lio_colorizer_set_params", params))) return rc;
+    h->p = *params;
+    return LIO_OK;
+}
+
+int lio_colorizer_set_cloud(lio_colorizer* h, const float* pts, int64_t n, int stride) {
+    const char* what = "lio_colorizer_set_cloud";
+    int rc = colorizer_handle(h, what);
+    if (rc) return rc;
+    if ((rc = cloud_arg(what, pts, n, stride))) return rc;
+    HIP_TRY(hipSetDevice(h->dev));
+    return status(lio::colorizer_set_cloud(h->c, pts, n, stride, h->st), what);
+}
+
+int lio_colorizer_add_frame(lio_colorizer* h, const lio_camera* cam, const double* Rt, const uint8_t* image, int64_t pitch,
+                            int64_t* n_updated) {
+    const std::string what = "lio_colorizer_add_frame";
+    int rc = colorizer_handle(h, what.c_str());
+    if (rc) return rc;
+    lio::CamArg a{};
+    if ((rc = camera_arg(what, cam, Rt, &a))) return rc;
+    if (!image) return fail(LIO_ERR_ARG, what + ": image is NULL");
+    if (!n_updated) return fail(LIO_ERR_ARG, what + ": n_updated is NULL");
+    if (pitch < 3 * (int64_t)cam->width) return fail(LIO_ERR_ARG, what + ": pitch must be at least 3 x width bytes");
+    if (!h->c.have_cloud) return fail(LIO_ERR_STATE, what + ": no cloud (call lio_colorizer_set_cloud first)");
+    *n_updated = 0;
+    HIP_TRY(hipSetDevice(h->dev));
+    return status(lio::colorizer_add_frame(h->c, a, image, pitch, h->p.bgr != 0, h->p.occlusion != 0, h->p.splat_radius,
+                                           h->p.depth_rel, h->p.depth_abs, n_updated, h->st),
+                  what.c_str());
+}
+
+int lio_colorizer_get(lio_colorizer* h, uint8_t* rgb, int32_t* frame_opt, double* depth_opt) {
+    int rc = colorizer_handle(h, "lio_colorizer_get");
+    if (rc) return rc;
+    if (!rgb) return fail(LIO_ERR_ARG, "lio_colorizer_get: rgb is NULL");
+    if (!h->c.have_cloud) return fail(LIO_ERR_STATE, "lio_colorizer_get: no cloud (call lio_colorizer_set_cloud first)");
+    HIP_TRY(hipSetDevice(h->dev));
+    return status(lio::colorizer_get(h->c, rgb, frame_opt, depth_opt, h->st), "lio_colorizer_get");
+}
+
+int lio_colorizer_reset(lio_colorizer* h) {
+    int rc = colorizer_handle(h, "lio_colorizer_reset");
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(h->dev));
+    return status(lio::colorizer_reset(h->c, h->st), "lio_colorizer_reset");
+}
+
+int lio_colorizer_get_timing(lio_colorizer* h, double* ms4) {
+    int rc = colorizer_handle(h, "lio_colorizer_get_timing");
+    if (rc) return rc;
+    if (!ms4) return fail(LIO_ERR_ARG, "lio_colorizer_get_timing: ms4 is NULL");
+    for (int k = 0; k < lio::kCzStages; ++k) ms4[k] = h->c.ms[k];
     return LIO_OK;
 }
 

@@ -1,0 +1,310 @@
+// lio_colorize.hip — camera projection and point cloud colorization from images on gfx950: the camera step of
+// the reference's offline leg (post_process/colorize_pcd.py:31-65; the projection role of
+// post_process/lidar_projection/src/lidar_projection.cpp:9-34; the 8-parameter rational model of
+// post_process/undistort_image.py:95-97), restated as IEEE double operations in a written order
+// (include/lio_gpu.h: lio_project_points, lio_colorizer_*).  The file is compiled with -ffp-contract=off, host
+// and device: no multiply-add is fused anywhere.
+//
+// One thread per point everywhere.  cz_project is the ONLY projection: the project, fused, splat and resolve
+// kernels all call it, so a point's pixel and depth are the same bits in every pass.
+//   without occlusion  cz_fused_kernel: project, gather the pixel, replace the state where zc < best_z
+//   with occlusion     cz_fill_kernel (the depth image to the bits of +inf) -> cz_splat_kernel (atomicMin of the
+//                      float depth's bits over the clipped splat) -> cz_resolve_kernel (project again, the
+//                      visibility test, gather, replace)
+// A float depth that is >= 0 orders as its bits do, so the minimum — and with it every output — does not depend
+// on the order in which the points arrive.  The splat reads a pixel before its atomic and skips the atomic when
+// the pixel already holds a depth that is not larger: the depth image only ever decreases, so a skipped atomic
+// would have changed nothing (a stale read only costs an atomic that changes nothing).
+#include <algorithm>
+#include <cstring>
+
+#include "lio_colorize.hpp"
+#include "lio_scratch.hpp"
+
+namespace lio {
+namespace {
+
+struct Projected {
+    double u, v, zc;
+    int px, py;  // -1 where invalid
+    bool valid;
+};
+
+// the contract's projection (include/lio_gpu.h, lio_project_points), one operation per line of it
+__device__ __forceinline__ Projected cz_project(const float* __restrict__ p, const CamArg& c) {
+    const double x = (double)p[0], y = (double)p[1], z = (double)p[2];
+    const double xc = ((c.R[0] * x + c.R[1] * y) + c.R[2] * z) + c.t[0];
+    const double yc = ((c.R[3] * x + c.R[4] * y) + c.R[5] * z) + c.t[1];
+    const double zc = ((c.R[6] * x + c.R[7] * y) + c.R[8] * z) + c.t[2];
+    const double xn = xc / zc, yn = yc / zc;
+    const double r2 = xn * xn + yn * yn;
+    const double num = 1.0 + ((c.k3 * r2 + c.k2) * r2 + c.k1) * r2;
+    const double den = 1.0 + ((c.k6 * r2 + c.k5) * r2 + c.k4) * r2;
+    const double rad = num / den;
+    const double a1 = (2.0 * xn) * yn, a2 = r2 + (2.0 * xn) * xn, a3 = r2 + (2.0 * yn) * yn;
+    const double xd = xn * rad + (c.p1 * a1 + c.p2 * a2);
+    const double yd = yn * rad + (c.p1 * a3 + c.p2 * a1);
+    Projected o;
+    o.u = c.fx * xd + c.cx;
+    o.v = c.fy * yd + c.cy;
+    o.zc = zc;
+    // every comparison is false on NaN
+    o.valid = zc > 0.0 && r2 <= c.r2_max && o.u >= 0.0 && o.u < (double)c.width && o.v >= 0.0 && o.v < (double)c.height;
+    o.px = o.valid ? (int)o.u : -1;  // truncation only after the test: u = -0.5 is invalid, not pixel 0
+    o.py = o.valid ? (int)o.v : -1;
+    return o;
+}
+
+__global__ __launch_bounds__(256) void cz_project_kernel(const float* __restrict__ pts, int64_t n, int stride, CamArg cam,
+                                                         double2* __restrict__ uv, double* __restrict__ zc,
+                                                         int2* __restrict__ pix, uint8_t* __restrict__ valid) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const Projected o = cz_project(pts + (size_t)i * stride, cam);
+    if (uv) uv[i] = make_double2(o.u, o.v);
+    if (zc) zc[i] = o.zc;
+    if (pix) pix[i] = make_int2(o.px, o.py);
+    valid[i] = o.valid ? 1 : 0;
+}
+
+__global__ __launch_bounds__(256) void cz_reset_kernel(double* __restrict__ best_z, uint8_t* __restrict__ rgb,
+                                                       int32_t* __restrict__ frame, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    best_z[i] = __longlong_as_double(0x7ff0000000000000ll);
+    rgb[3 * i] = rgb[3 * i + 1] = rgb[3 * i + 2] = 0;
+    frame[i] = -1;
+}
+
+// a candidate replaces the state iff zc < best_z (strict: on a tie the earlier frame stays); true when it did
+__device__ __forceinline__ bool cz_update(int64_t i, const Projected& o, const uint8_t* __restrict__ img, int64_t pitch,
+                                          bool bgr, int32_t frame_no, double* __restrict__ best_z, uint8_t* __restrict__ rgb,
+                                          int32_t* __restrict__ frame) {
+    if (!(o.zc < best_z[i])) return false;
+    const uint8_t* q = img + (size_t)o.py * (size_t)pitch + (size_t)o.px * 3;
+    const uint8_t c0 = q[0], c1 = q[1], c2 = q[2];
+    best_z[i] = o.zc;
+    rgb[3 * i] = bgr ? c2 : c0;
+    rgb[3 * i + 1] = c1;
+    rgb[3 * i + 2] = bgr ? c0 : c2;
+    frame[i] = frame_no;
+    return true;
+}
+
+// the frame's replacements: counted per workgroup, then one atomic per workgroup that has any (integer adds: the
+// total does not depend on their order).  Every thread of the workgroup calls it.
+__device__ __forceinline__ void cz_count(bool replaced, unsigned long long* __restrict__ count) {
+    const int c = __syncthreads_count(replaced ? 1 : 0);
+    if (threadIdx.x == 0 && c) atomicAdd(count, (unsigned long long)c);
+}
+
+__global__ __launch_bounds__(256) void cz_fused_kernel(const float* __restrict__ pts, int64_t n, int stride, CamArg cam,
+                                                       const uint8_t* __restrict__ img, int64_t pitch, bool bgr,
+                                                       int32_t frame_no, double* __restrict__ best_z,
+                                                       uint8_t* __restrict__ rgb, int32_t* __restrict__ frame,
+                                                       unsigned long long* __restrict__ count) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    bool replaced = false;
+    if (i < n) {
+        const Projected o = cz_project(pts + (size_t)i * stride, cam);
+        if (o.valid) replaced = cz_update(i, o, img, pitch, bgr, frame_no, best_z, rgb, frame);
+    }
+    cz_count(replaced, count);
+}
+
+__global__ __launch_bounds__(256) void cz_fill_kernel(uint4* __restrict__ d, int64_t n4, uint32_t pattern) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n4) d[i] = make_uint4(pattern, pattern, pattern, pattern);
+}
+
+__global__ __launch_bounds__(256) void cz_splat_kernel(const float* __restrict__ pts, int64_t n, int stride, CamArg cam,
+                                                       int radius, uint32_t* depth) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const Projected o = cz_project(pts + (size_t)i * stride, cam);
+    if (!o.valid) return;
+    const uint32_t zb = __float_as_uint((float)o.zc);
+    const int x0 = max(o.px - radius, 0), x1 = min(o.px + radius, cam.width - 1);
+    const int y0 = max(o.py - radius, 0), y1 = min(o.py + radius, cam.height - 1);
+    for (int qy = y0; qy <= y1; ++qy) {
+        uint32_t* row = depth + (size_t)qy * (size_t)cam.width;
+        for (int qx = x0; qx <= x1; ++qx)
+            if (row[qx] > zb) atomicMin(row + qx, zb);
+    }
+}
+
+__global__ __launch_bounds__(256) void cz_resolve_kernel(const float* __restrict__ pts, int64_t n, int stride, CamArg cam,
+                                                         const uint32_t* __restrict__ depth, float depth_rel,
+                                                         float depth_abs, const uint8_t* __restrict__ img, int64_t pitch,
+                                                         bool bgr, int32_t frame_no, double* __restrict__ best_z,
+                                                         uint8_t* __restrict__ rgb, int32_t* __restrict__ frame,
+                                                         unsigned long long* __restrict__ count) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    bool replaced = false;
+    if (i < n) {
+        const Projected o = cz_project(pts + (size_t)i * stride, cam);
+        if (o.valid) {
+            const float zf = (float)o.zc;
+            const float d = __uint_as_float(depth[(size_t)o.py * (size_t)cam.width + (size_t)o.px]);
+            const float bound = (d * (1.0f + depth_rel)) + depth_abs;
+            if (zf <= bound) replaced = cz_update(i, o, img, pitch, bgr, frame_no, best_z, rgb, frame);
+        }
+    }
+    cz_count(replaced, count);
+}
+
+// pinned host memory of at least `need` bytes, grown geometrically and counted
+int grow_pinned(uint8_t** p, size_t& bytes, size_t need) {
+    if (need <= bytes && *p) return kOk;
+    const size_t c = grown(need, bytes, (size_t)1 << 20);
+    if (*p) (void)hipHostFree(*p);
+    *p = nullptr;
+    bytes = 0;
+    count_alloc();
+    if (hipHostMalloc(reinterpret_cast<void**>(p), c, hipHostMallocDefault) != hipSuccess) {
+        *p = nullptr;
+        return kNoMem;
+    }
+    bytes = c;
+    return kOk;
+}
+
+}  // namespace
+
+void project_free(ProjectBuf& b) {
+    dev_free(&b.arena);
+    b = ProjectBuf{};
+}
+
+int project_points(ProjectBuf& b, const float* d_pts, int64_t n, int stride, const CamArg& cam, double* uv_opt,
+                   double* zc_opt, int32_t* pix_opt, uint8_t* valid, hipStream_t st) {
+    if (n <= 0) return kOk;
+    double2* d_uv = nullptr;
+    double* d_zc = nullptr;
+    int2* d_pix = nullptr;
+    uint8_t* d_valid = nullptr;
+    auto carve = [&](Carver& c) {
+        c(d_uv, uv_opt ? (size_t)n : 0);
+        c(d_zc, zc_opt ? (size_t)n : 0);
+        c(d_pix, pix_opt ? (size_t)n : 0);
+        c(d_valid, (size_t)n);
+    };
+    Carver measure;
+    carve(measure);
+    int rc = grow_scratch(&b.arena, b.arena_bytes, measure.bytes());
+    if (rc) return rc;
+    Carver assign(b.arena);
+    carve(assign);
+    if (!uv_opt) d_uv = nullptr;
+    if (!zc_opt) d_zc = nullptr;
+    if (!pix_opt) d_pix = nullptr;
+    cz_project_kernel<<<nblk(n), 256, 0, st>>>(d_pts, n, stride, cam, d_uv, d_zc, d_pix, d_valid);
+    LIO_HIP(hipGetLastError());
+    if (uv_opt) LIO_HIP(hipMemcpyAsync(uv_opt, d_uv, (size_t)n * sizeof(double2), hipMemcpyDeviceToHost, st));
+    if (zc_opt) LIO_HIP(hipMemcpyAsync(zc_opt, d_zc, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (pix_opt) LIO_HIP(hipMemcpyAsync(pix_opt, d_pix, (size_t)n * sizeof(int2), hipMemcpyDeviceToHost, st));
+    LIO_HIP(hipMemcpyAsync(valid, d_valid, (size_t)n, hipMemcpyDeviceToHost, st));
+    LIO_HIP(hipStreamSynchronize(st));
+    return kOk;
+}
+
+int colorizer_init(ColorizeBuf& c) {
+    count_alloc(2);
+    if (hipMalloc(reinterpret_cast<void**>(&c.count), sizeof(unsigned long long)) != hipSuccess) return kNoMem;
+    if (hipHostMalloc(reinterpret_cast<void**>(&c.h_count), sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess)
+        return kNoMem;
+    for (hipEvent_t& e : c.ev) LIO_HIP(hipEventCreate(&e));
+    return kOk;
+}
+
+void colorizer_free(ColorizeBuf& c) {
+    dev_free(&c.pts, &c.best_z, &c.rgb, &c.frame, &c.img, &c.depth, &c.count);
+    if (c.h_img) (void)hipHostFree(c.h_img);
+    if (c.h_count) (void)hipHostFree(c.h_count);
+    for (hipEvent_t e : c.ev)
+        if (e) (void)hipEventDestroy(e);
+    c = ColorizeBuf{};
+}
+
+int colorizer_reset(ColorizeBuf& c, hipStream_t st) {
+    c.frames = 0;
+    if (c.n > 0) {
+        cz_reset_kernel<<<nblk(c.n), 256, 0, st>>>(c.best_z, c.rgb, c.frame, c.n);
+        LIO_HIP(hipGetLastError());
+    }
+    LIO_HIP(hipStreamSynchronize(st));
+    return kOk;
+}
+
+int colorizer_set_cloud(ColorizeBuf& c, const float* pts, int64_t n, int stride, hipStream_t st) {
+    c.have_cloud = false;
+    c.n = 0;
+    int rc = grow_buf(&c.pts, c.pts_cap, std::max<int64_t>(n * stride, 1));
+    if (rc) return rc;
+    if (n > c.state_cap || !c.best_z) {
+        const int64_t cap = grown(std::max<int64_t>(n, 1), c.state_cap);
+        c.state_cap = 0;
+        rc = dev_alloc_all({dev_req(c.best_z, (size_t)cap), dev_req(c.rgb, (size_t)cap * 3), dev_req(c.frame, (size_t)cap)});
+        if (rc) return rc;
+        c.state_cap = cap;
+    }
+    if (n > 0) LIO_HIP(hipMemcpyAsync(c.pts, pts, (size_t)n * stride * sizeof(float), hipMemcpyHostToDevice, st));
+    c.n = n;
+    c.stride = stride;
+    rc = colorizer_reset(c, st);
+    if (rc) return rc;
+    c.have_cloud = true;
+    return kOk;
+}
+
+int colorizer_add_frame(ColorizeBuf& c, const CamArg& cam, const uint8_t* image, int64_t pitch, bool bgr, bool occlusion,
+                        int splat_radius, float depth_rel, float depth_abs, int64_t* n_updated, hipStream_t st) {
+    // the last row ends after its 3 * width bytes: nothing past it is read from the caller's buffer
+    const size_t bytes = (size_t)(cam.height - 1) * (size_t)pitch + (size_t)cam.width * 3;
+    const int64_t pixels = (int64_t)cam.width * cam.height;
+    const int64_t pixels4 = (pixels + 3) / 4;
+    int rc = grow_pinned(&c.h_img, c.h_img_bytes, bytes);
+    if (!rc) rc = grow_scratch(reinterpret_cast<void**>(&c.img), c.img_bytes, bytes);
+    if (!rc && occlusion) rc = grow_buf(&c.depth, c.depth_cap, pixels4 * 4);
+    if (rc) return rc;
+    const int32_t frame_no = c.frames;
+    LIO_HIP(hipEventRecord(c.ev[0], st));
+    std::memcpy(c.h_img, image, bytes);
+    LIO_HIP(hipMemcpyAsync(c.img, c.h_img, bytes, hipMemcpyHostToDevice, st));
+    LIO_HIP(hipMemsetAsync(c.count, 0, sizeof(unsigned long long), st));
+    LIO_HIP(hipEventRecord(c.ev[1], st));
+    if (occlusion && c.n > 0) {
+        cz_fill_kernel<<<nblk(pixels4), 256, 0, st>>>(reinterpret_cast<uint4*>(c.depth), pixels4, kCzInfBits);
+        LIO_HIP(hipEventRecord(c.ev[2], st));
+        cz_splat_kernel<<<nblk(c.n), 256, 0, st>>>(c.pts, c.n, c.stride, cam, splat_radius, c.depth);
+        LIO_HIP(hipEventRecord(c.ev[3], st));
+        cz_resolve_kernel<<<nblk(c.n), 256, 0, st>>>(c.pts, c.n, c.stride, cam, c.depth, depth_rel, depth_abs, c.img, pitch,
+                                                     bgr, frame_no, c.best_z, c.rgb, c.frame, c.count);
+    } else {
+        LIO_HIP(hipEventRecord(c.ev[2], st));
+        LIO_HIP(hipEventRecord(c.ev[3], st));
+        if (c.n > 0)
+            cz_fused_kernel<<<nblk(c.n), 256, 0, st>>>(c.pts, c.n, c.stride, cam, c.img, pitch, bgr, frame_no, c.best_z,
+                                                       c.rgb, c.frame, c.count);
+    }
+    LIO_HIP(hipGetLastError());
+    LIO_HIP(hipEventRecord(c.ev[kCzStages], st));
+    LIO_HIP(hipMemcpyAsync(c.h_count, c.count, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    LIO_HIP(hipStreamSynchronize(st));
+    for (int k = 0; k < kCzStages; ++k) LIO_HIP(hipEventElapsedTime(&c.ms[k], c.ev[k], c.ev[k + 1]));
+    c.frames = frame_no + 1;
+    *n_updated = (int64_t)*c.h_count;
+    return kOk;
+}
+
+int colorizer_get(ColorizeBuf& c, uint8_t* rgb, int32_t* frame_opt, double* depth_opt, hipStream_t st) {
+    if (c.n > 0) {
+        LIO_HIP(hipMemcpyAsync(rgb, c.rgb, (size_t)c.n * 3, hipMemcpyDeviceToHost, st));
+        if (frame_opt) LIO_HIP(hipMemcpyAsync(frame_opt, c.frame, (size_t)c.n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        if (depth_opt) LIO_HIP(hipMemcpyAsync(depth_opt, c.best_z, (size_t)c.n * sizeof(double), hipMemcpyDeviceToHost, st));
+    }
+    LIO_HIP(hipStreamSynchronize(st));
+    return kOk;
+}
+
+}  // namespace lio

@@ -56,6 +56,9 @@ EXPORTS = [
     "lio_sor_filter", "lio_radius_first_seed", "lio_denoise_slam_map", "lio_euclidean_clusters",
     "lio_segment_plane", "lio_plane_sample_triples", "lio_dbscan",
     "lio_gps_align", "lio_similarity2d_fit", "lio_georeference_xy",
+    "lio_abi_camera_struct_sizes", "lio_project_points", "lio_colorizer_create", "lio_colorizer_destroy",
+    "lio_colorizer_set_params", "lio_colorizer_set_cloud", "lio_colorizer_add_frame", "lio_colorizer_get",
+    "lio_colorizer_reset", "lio_colorizer_get_timing",
 ]
 
 
@@ -142,6 +145,16 @@ class KernelTiming(C.Structure):
 class DenoiseParams(C.Structure):
     _fields_ = [("seed_thres", C.c_float), ("cluster_seed_radius", C.c_float), ("denoise_radius", C.c_float),
                 ("noise_thres", C.c_float), ("mean_k", C.c_int), ("stddev_mul", C.c_float)]
+
+
+class Camera(C.Structure):
+    _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+                ("dist", C.c_double * 8), ("r2_max", C.c_double), ("width", C.c_int32), ("height", C.c_int32)]
+
+
+class ColorizeParams(C.Structure):
+    _fields_ = [("occlusion", C.c_int32), ("splat_radius", C.c_int32), ("depth_rel", C.c_float),
+                ("depth_abs", C.c_float), ("bgr", C.c_int32)]
 
 
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.POINTER(C.c_double), C.c_int64, C.POINTER(C.c_double), C.c_void_p)
@@ -233,6 +246,17 @@ def _declare(L):
         "lio_gps_align": (C.c_int, [vp, dp, C.c_int64, dp, C.c_int64, C.c_int, C.c_double, dp, C.POINTER(C.c_int32), dp]),
         "lio_similarity2d_fit": (C.c_int, [vp, dp, dp, C.c_int64, dp]),
         "lio_georeference_xy": (C.c_int, [vp, fp, C.c_int64, C.c_int, C.c_double, dp, dp, dp, fp, dp]),
+        "lio_abi_camera_struct_sizes": (C.c_int, [C.POINTER(C.c_int64), C.c_int]),
+        "lio_project_points": (C.c_int, [vp, fp, C.c_int64, C.c_int, C.POINTER(Camera), dp, dp, dp, C.POINTER(C.c_int32),
+                                         C.POINTER(C.c_uint8)]),
+        "lio_colorizer_create": (C.c_int, [C.c_int, C.POINTER(ColorizeParams), C.POINTER(vp)]),
+        "lio_colorizer_destroy": (C.c_int, [vp]),
+        "lio_colorizer_set_params": (C.c_int, [vp, C.POINTER(ColorizeParams)]),
+        "lio_colorizer_set_cloud": (C.c_int, [vp, fp, C.c_int64, C.c_int]),
+        "lio_colorizer_add_frame": (C.c_int, [vp, C.POINTER(Camera), dp, vp, C.c_int64, C.POINTER(C.c_int64)]),
+        "lio_colorizer_get": (C.c_int, [vp, C.POINTER(C.c_uint8), C.POINTER(C.c_int32), dp]),
+        "lio_colorizer_reset": (C.c_int, [vp]),
+        "lio_colorizer_get_timing": (C.c_int, [vp, dp]),
         "lio_ctx_create": (C.c_int, [vp, C.POINTER(MatchParams), C.POINTER(vp)]),
         "lio_ctx_destroy": (C.c_int, [vp]),
         "lio_scan_set": (C.c_int, [vp, fp, C.c_int64]),
@@ -331,6 +355,8 @@ def lib():
 # the ctypes mirrors of lio_abi_struct_sizes' structs, in its order
 _ABI_STRUCTS = ("MapParams", "MatchParams", "Pose", "State", "IeskfParams", "IeskfStats", "IcpParams", "IcpResult",
                 "LocalMap", "IncrementalStats", "ImuPose", "ScanPrepParams", "CloudField", "KernelTiming", "DenoiseParams")
+# likewise of lio_abi_camera_struct_sizes (the first list is closed: callers compare its length)
+_ABI_CAMERA_STRUCTS = ("Camera", "ColorizeParams")
 
 
 def _check_abi(L):
@@ -344,6 +370,15 @@ def _check_abi(L):
     if n != len(mine) or list(sizes) != mine:
         raise ImportError(f"{LIB_PATH}: ABI mismatch with lio_gpu/_capi.py — library struct sizes {list(sizes)}, "
                           f"binding {mine} ({', '.join(_ABI_STRUCTS)})")
+    if not hasattr(L, "lio_abi_camera_struct_sizes"):  # an older build (LIO_GPU_LIB) has no camera entry points
+        return
+    n = int(L.lio_abi_camera_struct_sizes(None, 0))
+    sizes = (C.c_int64 * n)()
+    L.lio_abi_camera_struct_sizes(sizes, n)
+    mine = [C.sizeof(globals()[k]) for k in _ABI_CAMERA_STRUCTS]
+    if n != len(mine) or list(sizes) != mine:
+        raise ImportError(f"{LIB_PATH}: ABI mismatch with lio_gpu/_capi.py — library struct sizes {list(sizes)}, "
+                          f"binding {mine} ({', '.join(_ABI_CAMERA_STRUCTS)})")
 
 
 def check(rc):

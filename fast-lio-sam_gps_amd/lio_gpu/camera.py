@@ -1,0 +1,269 @@
+"""Camera projection and point cloud colorization from images: the camera step of the reference's offline leg
+over the C-ABI.
+
+* :class:`CameraModel` — pinhole intrinsics, OpenCV's 8-parameter rational distortion model
+  (post_process/undistort_image.py:95-97) and the image size
+* :func:`project_points` — the projection of post_process/colorize_pcd.py:31-47 (``lio_project_points``)
+* :class:`Colorizer` — colours of a cloud from any number of frames, with an opt-in z-buffer (``lio_colorizer_*``)
+* :func:`pack_rgb` — PCL's packed ``rgb`` field; :func:`colorize_pcd` — ``colorize_pcd.py`` on files
+* :func:`world_to_camera` — the ``Rt`` of a keyframe from its pose and the LiDAR-to-camera extrinsic
+
+Images are numpy arrays (``height x width x 3`` uint8); decoding them is the caller's.  Every result follows the
+contract of include/lio_gpu.h bit for bit: IEEE double operations in a written order, nothing fused.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from dataclasses import dataclass, field
+
+import numpy as np
+
+from . import _capi
+from ._capi import check, lib
+from .filters import _Handle, _fp, _rows
+
+_dp = C.POINTER(C.c_double)
+
+
+@dataclass
+class CameraModel:
+    """``dist``: ``k1 k2 p1 p2 [k3 [k4 k5 k6]]`` in OpenCV's order (4, 5 or 8 numbers; none: a pinhole).
+    ``r2_max`` bounds the squared normalised radius ``xn^2 + yn^2`` of a valid point (``inf``: no limit)."""
+    fx: float
+    fy: float
+    cx: float
+    cy: float
+    width: int
+    height: int
+    dist: tuple = field(default_factory=tuple)
+    r2_max: float = math.inf
+
+    def __post_init__(self):
+        d = np.asarray(self.dist, np.float64).ravel()
+        if len(d) not in (0, 4, 5, 8):
+            raise ValueError("CameraModel: dist takes 0, 4, 5 or 8 coefficients (k1 k2 p1 p2 k3 k4 k5 k6)")
+        self.dist = tuple(float(v) for v in np.concatenate([d, np.zeros(8 - len(d))]))
+        for name in ("fx", "fy", "cx", "cy"):
+            setattr(self, name, float(getattr(self, name)))
+            if not math.isfinite(getattr(self, name)):
+                raise ValueError(f"CameraModel: {name} is not finite")
+        if not all(math.isfinite(v) for v in self.dist):
+            raise ValueError("CameraModel: a distortion coefficient is not finite")
+        self.r2_max = float(self.r2_max)
+        if not self.r2_max >= 0.0:
+            raise ValueError("CameraModel: r2_max must be >= 0 (inf: no limit) and not NaN")
+        if int(self.width) != self.width or int(self.height) != self.height or self.width < 1 or self.height < 1:
+            raise ValueError("CameraModel: width and height must be integers of at least 1")
+        self.width, self.height = int(self.width), int(self.height)
+        if self.width * self.height >= 1 << 31:
+            raise ValueError("CameraModel: width x height must be below 2^31")
+
+    def _c(self) -> _capi.Camera:
+        return _capi.Camera(self.fx, self.fy, self.cx, self.cy, (C.c_double * 8)(*self.dist), self.r2_max, self.width,
+                            self.height)
+
+
+def _pose(Rt) -> np.ndarray:
+    """12 doubles, row-major R then t, from 12 numbers, a 3 x 4 ``[R | t]`` or a 4 x 4 homogeneous matrix"""
+    a = np.asarray(Rt, np.float64)
+    if a.shape == (4, 4):
+        a = a[:3]
+    if a.shape == (3, 4):
+        a = np.concatenate([a[:, :3].ravel(), a[:, 3]])
+    if a.shape != (12,):
+        raise ValueError("Rt: 12 numbers (row-major R, then t), a 3 x 4 [R | t] or a 4 x 4 matrix is expected")
+    return np.ascontiguousarray(a)
+
+
+def world_to_camera(T_world_lidar, T_cam_lidar) -> np.ndarray:
+    """The ``Rt`` (12 doubles) that maps MAP points to the camera frame of one keyframe: ``T_cam_lidar @
+    inv(T_world_lidar)``, with the keyframe's pose ``T_world_lidar`` (LiDAR to world) and the rig's extrinsic
+    ``T_cam_lidar`` (LiDAR to camera), both 4 x 4 rigid transforms.  A host helper in double: the inverse is the
+    transpose form ``[R^T | -R^T t]``, not a general matrix inverse."""
+    Tw, Tc = np.asarray(T_world_lidar, np.float64), np.asarray(T_cam_lidar, np.float64)
+    if Tw.shape != (4, 4) or Tc.shape != (4, 4):
+        raise ValueError("world_to_camera: two 4 x 4 transforms are expected")
+    Rw, tw, Rc, tc = Tw[:3, :3], Tw[:3, 3], Tc[:3, :3], Tc[:3, 3]
+    R = Rc @ Rw.T
+    t = tc - R @ tw
+    return np.concatenate([R.ravel(), t])
+
+
+@dataclass
+class Projection:
+    """``uv``: n x 2 doubles; ``zc``: the depth along the optical axis; ``pix``: n x 2 int32 ``(px, py)``, -1 where
+    the point is not valid; ``valid``: the script's mask"""
+    uv: np.ndarray
+    zc: np.ndarray
+    pix: np.ndarray
+    valid: np.ndarray
+
+
+def project_points(pts, camera: CameraModel, Rt, handle: _Handle | None = None) -> Projection:
+    """Point records (n x stride float32, x, y, z first) through ``Rt`` and the camera, by the contract of
+    ``lio_project_points``: with no distortion ``u`` is bit for bit ``fx * (x / z) + cx`` of colorize_pcd.py:39."""
+    h = handle or _Handle()
+    p = _rows(pts)
+    n = len(p)
+    rt = _pose(Rt)
+    uv, zc = np.zeros((n, 2), np.float64), np.zeros(n, np.float64)
+    pix, valid = np.zeros((n, 2), np.int32), np.zeros(n, np.uint8)
+    cam = camera._c()
+    check(lib().lio_project_points(h._h, _fp(p), n, p.shape[1], C.byref(cam), rt.ctypes.data_as(_dp), uv.ctypes.data_as(_dp),
+                                   zc.ctypes.data_as(_dp), pix.ctypes.data_as(C.POINTER(C.c_int32)),
+                                   valid.ctypes.data_as(C.POINTER(C.c_uint8))))
+    return Projection(uv, zc, pix, valid.astype(bool))
+
+
+def _image(image, camera: CameraModel):
+    """(array kept alive, row pitch in bytes) of a height x width x 3 uint8 image; a view whose pixels are packed
+    (rows may be padded) is passed as it is, anything else is copied"""
+    a = np.asarray(image)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError("image: a height x width x 3 uint8 array is expected")
+    if a.shape[:2] != (camera.height, camera.width):
+        raise ValueError(f"image: shape {a.shape[:2]} is not the camera's (height, width) = {(camera.height, camera.width)}")
+    if a.strides[2] != 1 or a.strides[1] != 3 or a.strides[0] < 3 * camera.width:
+        a = np.ascontiguousarray(a)
+    return a, a.strides[0]
+
+
+class Colorizer:
+    """Colours of a cloud from camera frames: ``set_cloud`` once, ``add_frame`` per image; per point the nearest
+    view wins (the smallest depth ``zc``; on a tie the earlier frame).  ``occlusion=False`` is the reference
+    (colorize_pcd.py has none: points behind a wall take the wall's colour); ``occlusion=True`` builds a z-buffer
+    per frame — every valid point splats its float depth over ``(2 splat_radius + 1)^2`` pixels — and colours a
+    point only if ``zf <= D * (1 + depth_rel) + depth_abs`` at its own pixel.  ``bgr``: the image's channel order is
+    OpenCV's (as in the script); the state is always R G B."""
+
+    def __init__(self, occlusion: bool = False, splat_radius: int = 0, depth_rel: float = 0.0, depth_abs: float = 0.0,
+                 bgr: bool = True, device: int = 0):
+        self._h = C.c_void_p()
+        self._n = 0
+        p = _capi.ColorizeParams(int(bool(occlusion)), int(splat_radius), float(depth_rel), float(depth_abs), int(bool(bgr)))
+        check(lib().lio_colorizer_create(device, C.byref(p), C.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            lib().lio_colorizer_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_params(self, occlusion: bool = False, splat_radius: int = 0, depth_rel: float = 0.0, depth_abs: float = 0.0,
+                   bgr: bool = True):
+        p = _capi.ColorizeParams(int(bool(occlusion)), int(splat_radius), float(depth_rel), float(depth_abs), int(bool(bgr)))
+        check(lib().lio_colorizer_set_params(self._h, C.byref(p)))
+
+    def set_cloud(self, pts):
+        p = _rows(pts)
+        check(lib().lio_colorizer_set_cloud(self._h, _fp(p), len(p), p.shape[1]))
+        self._n = len(p)
+
+    def add_frame(self, camera: CameraModel, Rt, image) -> int:
+        """one frame; returns the number of points whose colour it replaced"""
+        img, pitch = _image(image, camera)
+        rt = _pose(Rt)
+        cam = camera._c()
+        n = C.c_int64(0)
+        check(lib().lio_colorizer_add_frame(self._h, C.byref(cam), rt.ctypes.data_as(_dp), img.ctypes.data_as(C.c_void_p), pitch,
+                                            C.byref(n)))
+        return int(n.value)
+
+    def reset(self):
+        check(lib().lio_colorizer_reset(self._h))
+
+    def state(self):
+        """(rgb n x 3 uint8, frame n int32, depth n float64) in one download"""
+        n = max(self._n, 1)
+        rgb, frame, depth = np.zeros((n, 3), np.uint8), np.zeros(n, np.int32), np.zeros(n, np.float64)
+        check(lib().lio_colorizer_get(self._h, rgb.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                      frame.ctypes.data_as(C.POINTER(C.c_int32)), depth.ctypes.data_as(_dp)))
+        return rgb[:self._n], frame[:self._n], depth[:self._n]
+
+    @property
+    def rgb(self) -> np.ndarray:
+        return self.state()[0]
+
+    @property
+    def frame(self) -> np.ndarray:
+        """per point the number of the frame that coloured it, -1: none (``frame >= 0`` is the script's mask)"""
+        return self.state()[1]
+
+    @property
+    def depth(self) -> np.ndarray:
+        """per point the depth ``zc`` in the frame that coloured it, ``inf``: none"""
+        return self.state()[2]
+
+    def colors_float(self) -> np.ndarray:
+        """the script's n x 3 double colours: ``rgb / 255.0``, grey 0.5 where no frame saw the point"""
+        rgb, frame, _ = self.state()
+        return colors_float(rgb, frame)
+
+    def timing(self) -> dict:
+        """device ms of the last frame: upload (staging copy included), fill, splat, resolve (or the fused kernel)"""
+        ms = np.zeros(4, np.float64)
+        check(lib().lio_colorizer_get_timing(self._h, ms.ctypes.data_as(_dp)))
+        return dict(zip(("upload_ms", "fill_ms", "splat_ms", "resolve_ms"), (float(v) for v in ms)))
+
+
+def colors_float(rgb, frame) -> np.ndarray:
+    """colorize_pcd.py:58-63: ``colors[:] = 0.5; colors[valid] = img[v, u, ::-1] / 255.0``"""
+    rgb = np.asarray(rgb, np.uint8)
+    out = np.full(rgb.shape, 0.5, np.float64)
+    seen = np.asarray(frame) >= 0
+    out[seen] = rgb[seen] / 255.0
+    return out
+
+
+def pack_rgb(rgb) -> np.ndarray:
+    """n x 3 uint8 (r, g, b) -> PCL's packed ``rgb`` field: the uint32 ``r << 16 | g << 8 | b`` seen as float32"""
+    c = np.asarray(rgb)
+    if c.dtype != np.uint8 or c.ndim != 2 or c.shape[1] != 3:
+        raise ValueError("pack_rgb: an n x 3 uint8 array is expected")
+    c = c.astype(np.uint32)
+    return ((c[:, 0] << 16) | (c[:, 1] << 8) | c[:, 2]).astype(np.uint32).view(np.float32)
+
+
+def _read_xyz(path: str) -> np.ndarray:
+    """x y z of a PCD file"""
+    from . import formats
+
+    codec = formats.CloudCodec()
+    try:
+        return codec.read_pcd(path, want=("x", "y", "z"))
+    finally:
+        codec.close()
+
+
+def _compute(xyz, image, camera, Rt, **params):
+    """one cloud against one image: (rgb, frame)"""
+    cz = Colorizer(**params)
+    try:
+        cz.set_cloud(xyz)
+        cz.add_frame(camera, Rt, image)
+        rgb, frame, _ = cz.state()
+        return rgb, frame
+    finally:
+        cz.close()
+
+
+def colorize_pcd(in_path: str, image, camera: CameraModel, Rt, out_path: str, default_rgb=(128, 128, 128), **params):
+    """``colorize_pcd.py`` on files: x y z of ``in_path`` coloured from one image, written as a binary PCD with the
+    fields ``x y z rgb`` (PCL's packed float).  Points outside the image take ``default_rgb`` (the script's grey).
+    ``params``: :class:`Colorizer`'s.  Returns (points, coloured points)."""
+    from . import formats
+
+    xyz = _read_xyz(in_path)
+    rgb, frame = _compute(xyz, image, camera, Rt, **params)
+    rgb = np.where((np.asarray(frame) >= 0)[:, None], rgb, np.asarray(default_rgb, np.uint8)[None, :]).astype(np.uint8)
+    rec = np.empty((len(xyz), 4), np.float32)
+    rec[:, :3] = xyz
+    rec[:, 3] = pack_rgb(rgb)
+    formats.write_pcd_binary(out_path, rec, names=("x", "y", "z", "rgb"))
+    return len(xyz), int(np.count_nonzero(np.asarray(frame) >= 0))

@@ -715,6 +715,94 @@ int lio_similarity2d_fit(lio_filter* f, const double* src_xy, const double* dst_
 int lio_georeference_xy(lio_filter* f, const float* pts, int64_t n, int stride, double scale, const double* R4,
                         const double* t2, const double* origin2_opt, float* out, double* xy_out_opt);
 
+/* ------------------------------- camera projection and point cloud colorization from images (offline camera leg) */
+/* A camera: pinhole intrinsics, the 8-parameter rational distortion model of OpenCV (post_process/
+ * undistort_image.py:95-97) and the image size.  dist = k1 k2 p1 p2 k3 k4 k5 k6; all zero is a pinhole.  r2_max
+ * bounds the squared normalised radius (+inf: no limit): a rational model is only meaningful inside the field it
+ * was calibrated on, and a far-off-axis point can fold back into the image beyond it.                            */
+typedef struct lio_camera {
+    double fx, fy, cx, cy;
+    double dist[8];
+    double r2_max;
+    int32_t width, height;
+} lio_camera;
+/* occlusion: 0 (the reference: none) or 1 (the z-buffer below); splat_radius 0..8; depth_rel, depth_abs >= 0:
+ * the visibility tolerance; bgr: 1 when the image's channel order is B G R (OpenCV's, as in the script), 0 for
+ * R G B.  NULL where a function takes these means {0, 0, 0, 0, 1}.                                               */
+typedef struct lio_colorize_params {
+    int32_t occlusion;
+    int32_t splat_radius;
+    float depth_rel;
+    float depth_abs;
+    int32_t bgr;
+} lio_colorize_params;
+/* sizeof of the two structs above, in that order, as lio_abi_struct_sizes does for the earlier ones (whose list
+ * is closed: callers compare its length); returns their number.                                                  */
+int lio_abi_camera_struct_sizes(int64_t* out, int n);
+
+/* The projection of post_process/colorize_pcd.py:31-47 (projectPointsToImagePlane's role in post_process/
+ * lidar_projection/src/lidar_projection.cpp:9-34) on point records (n x stride floats, x, y, z first; stride
+ * 3..8; 0 <= n < 2^31).  Rt: 12 doubles, row-major 3 x 3 R, then t; it maps points to the camera frame.  This is
+ * the library's own restatement, exact to the bit: per point, in IEEE double, nothing fused, in this order:
+ *   x, y, z widened to double;
+ *   c_k = ((R[k][0] x + R[k][1] y) + R[k][2] z) + t[k] for the rows k of R: xc, yc, zc;
+ *   xn = xc / zc; yn = yc / zc; r2 = xn xn + yn yn;
+ *   num = 1 + ((k3 r2 + k2) r2 + k1) r2; den = 1 + ((k6 r2 + k5) r2 + k4) r2; rad = num / den;
+ *   a1 = 2 xn yn; a2 = r2 + 2 xn xn; a3 = r2 + 2 yn yn;
+ *   xd = xn rad + (p1 a1 + p2 a2); yd = yn rad + (p1 a3 + p2 a1);
+ *   u = fx xd + cx; v = fy yd + cy;
+ *   valid = zc > 0 && r2 <= r2_max && u >= 0 && u < width && v >= 0 && v < height (EVERY COMPARISON IS FALSE ON
+ *   NaN: the script's test, colorize_pcd.py:47, with r2_max added);
+ *   px = (int)u; py = (int)v: TRUNCATION ONLY AFTER THE TEST (u = -0.5 is invalid, it is not pixel 0).
+ * With an all-zero dist, rad == 1 and the tangential term is +0, so u is bit for bit the script's fx * (x / z) +
+ * cx.  The script's R @ P.T + t goes through BLAS and differs from this fixed order in the last bits of some
+ * coordinates; the C++ tool's float formulation (K p) / p_z is another rounding and is NOT reproduced.
+ * uv_opt (n x 2 doubles: u, v), zc_opt (n doubles), pix_opt (n x 2 int32: px, py, -1 -1 where invalid) may be
+ * NULL; valid: n uint8.  LIO_ERR_ARG before any device work, with a message that names the bound: a NULL cam, Rt
+ * or valid, NULL pts with n > 0, n < 0 or >= 2^31, stride outside 3..8, width or height below 1, width x height >=
+ * 2^31, a non-finite intrinsic, distortion or pose entry, r2_max NaN or negative.                                */
+int lio_project_points(lio_filter* f, const float* pts, int64_t n, int stride, const lio_camera* cam, const double* Rt,
+                       double* uv_opt, double* zc_opt, int32_t* pix_opt, uint8_t* valid);
+
+/* Colours of a point cloud from any number of camera frames.  The cloud and the per-point state stay on the
+ * device between frames; a frame uploads its image and 12 + 16 doubles.  Per-point state: best_z (double, starts
+ * at +inf), rgb (3 x uint8, starts at 0), frame (int32, starts at -1).
+ *   frame     a frame's CANDIDATES are its valid points (lio_project_points); with occlusion, the visible ones.
+ *             A candidate replaces the state iff zc < best_z — STRICT, SO ON A TIE THE EARLIER FRAME STAYS — and
+ *             the state takes zc, the colour of pixel (px, py) IN R G B ORDER whatever the image's order, and the
+ *             running frame number (0 for the first frame after set_cloud or reset).
+ *   occlusion (opt-in; the reference has none: points behind a wall take the wall's colour) a depth image D of
+ *             width x height uint32 starts at the bits of float +inf; every valid point has zf = (float)zc, rounded
+ *             to nearest, and writes D[q] = min(D[q], bits(zf)) for every pixel q = (px + dx, py + dy) with |dx|,
+ *             |dy| <= splat_radius inside the image.  zf >= 0, so unsigned order on the bits is float order and the
+ *             minimum does not depend on the order of arrival.  A valid point is VISIBLE iff
+ *             zf <= (D[py][px] * (1.0f + depth_rel)) + depth_abs, in float, nothing fused.  A point always sees its
+ *             own splat; it is hidden only by something in front of it by more than the tolerance.
+ * With one frame and no occlusion this is colorize_pcd.py: frame >= 0 is its mask, rgb / 255.0 (0.5 where frame <
+ * 0) its double colours bit for bit.  Blending of several frames is out of scope: the nearest view wins.
+ * image: height rows of `pitch` bytes, 3 bytes per pixel; only 3 x width bytes of the last row are read.
+ * LIO_ERR_ARG before any device work, with a message that names the bound: a NULL pointer (frame_opt and depth_opt
+ * excepted; pts may be NULL when n == 0), n < 0 or >= 2^31, stride outside 3..8, the camera and pose conditions of
+ * lio_project_points, pitch < 3 x width, splat_radius outside 0..8, a negative or non-finite tolerance.
+ * LIO_ERR_STATE: add_frame or get before set_cloud.  Repeated sequences give identical bits; from the second frame
+ * of one size on nothing is allocated (lio_alloc_count).                                                          */
+typedef struct lio_colorizer lio_colorizer;
+int lio_colorizer_create(int device, const lio_colorize_params* params, lio_colorizer** out);
+int lio_colorizer_destroy(lio_colorizer* h);
+int lio_colorizer_set_params(lio_colorizer* h, const lio_colorize_params* params);
+/* uploads the cloud, resets the state and the frame number */
+int lio_colorizer_set_cloud(lio_colorizer* h, const float* pts, int64_t n, int stride);
+/* n_updated: the number of points whose state this frame replaced */
+int lio_colorizer_add_frame(lio_colorizer* h, const lio_camera* cam, const double* Rt, const uint8_t* image, int64_t pitch,
+                            int64_t* n_updated);
+/* rgb: n x 3 uint8; frame_opt: n int32 (-1: never coloured); depth_opt: n doubles (best_z, +inf likewise) */
+int lio_colorizer_get(lio_colorizer* h, uint8_t* rgb, int32_t* frame_opt, double* depth_opt);
+/* the state back to its start; the cloud stays */
+int lio_colorizer_reset(lio_colorizer* h);
+/* device time of the last add_frame in ms (stream events): upload (staging copy included), depth fill, splat,
+ * resolve (without occlusion: 0, 0 and the fused kernel)                                                          */
+int lio_colorizer_get_timing(lio_colorizer* h, double* ms4);
+
 /* ------------------------------------------- wire / disk formats (§8(f) row 4) */
 /* One output column of a packed point record: byte offset, sensor_msgs/PointField datatype
  * (INT8 1, UINT8 2, INT16 3, UINT16 4, INT32 5, UINT32 6, FLOAT32 7, FLOAT64 8; 0 = absent -> 0)

@@ -25,6 +25,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <limits>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -784,6 +785,96 @@ void georeference(FilterGPU& f, const std::vector<PointT>& in, const Similarity2
                               R4, T.t, origin, reinterpret_cast<float*>(out.data()), xy_opt ? xy_opt->data() : nullptr),
           "georeference");
 }
+
+// A camera (lio_camera): pinhole intrinsics, OpenCV's rational distortion k1 k2 p1 p2 k3 k4 k5 k6 (all zero: a
+// pinhole), a bound on the squared normalised radius (+inf: none) and the image size.
+struct CameraModel {
+    double fx = 1.0, fy = 1.0, cx = 0.0, cy = 0.0;
+    std::array<double, 8> dist{};
+    double r2_max = std::numeric_limits<double>::infinity();
+    int width = 1, height = 1;
+    lio_camera c() const {
+        lio_camera o{};
+        o.fx = fx, o.fy = fy, o.cx = cx, o.cy = cy;
+        for (size_t k = 0; k < 8; ++k) o.dist[k] = dist[k];
+        o.r2_max = r2_max;
+        o.width = width, o.height = height;
+        return o;
+    }
+};
+
+// what project_points returns per point: u, v (doubles), zc, px, py (-1 where invalid) and the mask
+struct Projection {
+    std::vector<double> uv, zc;
+    std::vector<int32_t> pix;
+    std::vector<uint8_t> valid;
+};
+
+// The projection of post_process/colorize_pcd.py:31-47 (projectPointsToImagePlane's role in the C++ tool) by the
+// contract of lio_project_points.  Rt: row-major 3 x 3 R, then t; it maps the points to the camera frame.
+template <typename PointT>
+void project_points(FilterGPU& f, const std::vector<PointT>& in, const CameraModel& cam, const std::array<double, 12>& Rt,
+                    Projection& out) {
+    const int64_t n = (int64_t)in.size();
+    out.uv.assign(2 * in.size(), 0.0);
+    out.zc.assign(in.size(), 0.0);
+    out.pix.assign(2 * in.size(), -1);
+    out.valid.assign(in.size(), 0);
+    const lio_camera c = cam.c();
+    uint8_t none = 0;  // a non-NULL valid for an empty cloud
+    check(lio_project_points(f.handle(), reinterpret_cast<const float*>(in.data()), n, float_stride<PointT>(), &c, Rt.data(),
+                             out.uv.data(), out.zc.data(), out.pix.data(), n ? out.valid.data() : &none),
+          "project_points");
+}
+
+// Colours of a cloud from camera frames (lio_colorizer), in the shape of the filters: setInputCloud / addFrame /
+// colors / reset.  The nearest view of a point wins; occlusion is opt-in (the reference has none).
+template <typename PointT>
+class Colorizer {
+public:
+    explicit Colorizer(int device = 0) { check(lio_colorizer_create(device, nullptr, &h_), "lio_colorizer_create"); }
+    ~Colorizer() { lio_colorizer_destroy(h_); }
+    Colorizer(const Colorizer&) = delete;
+    Colorizer& operator=(const Colorizer&) = delete;
+    void setOcclusion(bool on, int splat_radius = 0, float depth_rel = 0.f, float depth_abs = 0.f) {
+        p_.occlusion = on ? 1 : 0, p_.splat_radius = splat_radius, p_.depth_rel = depth_rel, p_.depth_abs = depth_abs;
+        check(lio_colorizer_set_params(h_, &p_), "Colorizer::setOcclusion");
+    }
+    // the image's channel order: B G R (OpenCV's, the default) or R G B
+    void setBgr(bool bgr) {
+        p_.bgr = bgr ? 1 : 0;
+        check(lio_colorizer_set_params(h_, &p_), "Colorizer::setBgr");
+    }
+    void setInputCloud(const std::vector<PointT>* cloud) {
+        if (!cloud) throw Error(LIO_ERR_ARG, "Colorizer: no input cloud");
+        check(lio_colorizer_set_cloud(h_, reinterpret_cast<const float*>(cloud->data()), (int64_t)cloud->size(),
+                                      float_stride<PointT>()),
+              "Colorizer::setInputCloud");
+        n_ = cloud->size();
+    }
+    // image: height rows of `pitch` bytes (0: 3 * width), 3 bytes per pixel; returns the points it re-coloured
+    int64_t addFrame(const CameraModel& cam, const std::array<double, 12>& Rt, const uint8_t* image, int64_t pitch = 0) {
+        const lio_camera c = cam.c();
+        int64_t updated = 0;
+        check(lio_colorizer_add_frame(h_, &c, Rt.data(), image, pitch ? pitch : 3 * (int64_t)cam.width, &updated),
+              "Colorizer::addFrame");
+        return updated;
+    }
+    // rgb: n x 3 (r, g, b); frame: per point the frame that coloured it, -1: none; depth_opt: its zc, +inf: none
+    void colors(std::vector<uint8_t>& rgb, std::vector<int32_t>& frame, std::vector<double>* depth_opt = nullptr) {
+        rgb.assign(3 * n_ + 1, 0);  // one spare byte: a non-NULL rgb for an empty cloud
+        frame.assign(n_, -1);
+        if (depth_opt) depth_opt->assign(n_, 0.0);
+        check(lio_colorizer_get(h_, rgb.data(), frame.data(), depth_opt ? depth_opt->data() : nullptr), "Colorizer::colors");
+        rgb.resize(3 * n_);
+    }
+    void reset() { check(lio_colorizer_reset(h_), "Colorizer::reset"); }
+
+private:
+    lio_colorizer* h_ = nullptr;
+    lio_colorize_params p_{0, 0, 0.f, 0.f, 1};
+    size_t n_ = 0;
+};
 
 // Open3D's PointCloud::SegmentPlane as the offline pipeline calls it (post_process/clustering.py:21-28), in the
 // shape of pcl::SACSegmentation: setInputCloud / setDistanceThreshold / setMaxIterations / setSeed / segment.
