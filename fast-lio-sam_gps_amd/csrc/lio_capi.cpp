@@ -25,6 +25,7 @@
 #include "lio_cluster.hpp"
 #include "lio_dbscan.hpp"
 #include "lio_colorize.hpp"
+#include "lio_undistort.hpp"
 #include "lio_gpsalign.hpp"
 #include "lio_plane.hpp"
 #include "lio_pool.hpp"
@@ -1086,7 +1087,7 @@ struct lio_filter {
     lio::ClusterBuf cl;  // lio_euclidean_clusters, lio_dbscan (with dn: the grid, the sorts and the scan)
     lio::PlaneBuf pl;    // lio_segment_plane (with dn: the flags and the scan)
     lio::GpsAlignBuf ga; // lio_gps_align, lio_similarity2d_fit, lio_georeference_xy
-    lio::ProjectBuf pj;  // lio_project_points
+    lio::ProjectBuf pj;  // lio_project_points, lio_undistort_map
 };
 
 static lio::UndistortEnd undistort_end(const lio_pose* e) {
@@ -1716,6 +1717,128 @@ int lio_colorizer_get_timing(lio_colorizer* h, double* ms4) {
     if (rc) return rc;
     if (!ms4) return fail(LIO_ERR_ARG, "lio_colorizer_get_timing: ms4 is NULL");
     for (int k = 0; k < lio::kCzStages; ++k) ms4[k] = h->c.ms[k];
+    return LIO_OK;
+}
+
+// ---- image undistortion (lio_undistort.hip) ----
+// The camera checks shared by lio_undistort_map and lio_undistorter_set_camera; they need no device and come before
+// the handle is looked at.  dst_opt NULL: src's intrinsics and size.
+static int undistort_cams_arg(const std::string& what, const lio_camera* src, const lio_camera* dst_opt, lio::CamArg* a,
+                              lio::UdDst* d) {
+    if (!src) return fail(LIO_ERR_ARG, what + ": src is NULL");
+    const lio_camera* dst = dst_opt ? dst_opt : src;
+    for (const lio_camera* c : {src, dst})
+        if (c->width < 1 || c->width > lio::kUdMaxSize || c->height < 1 || c->height > lio::kUdMaxSize)
+            return fail(LIO_ERR_ARG, what + ": width and height must be in 1..32767");
+    const double k[8] = {src->fx, src->fy, src->cx, src->cy, dst->fx, dst->fy, dst->cx, dst->cy};
+    if (!all_finite(k, 8)) return fail(LIO_ERR_ARG, what + ": an intrinsic (fx, fy, cx, cy) is not finite");
+    if (!all_finite(src->dist, 8)) return fail(LIO_ERR_ARG, what + ": a distortion coefficient is not finite");
+    if (dst->fx == 0.0 || dst->fy == 0.0) return fail(LIO_ERR_ARG, what + ": dst fx and fy must not be 0");
+    if (dst_opt)
+        for (double v : dst_opt->dist)
+            if (!(v == 0.0)) return fail(LIO_ERR_ARG, what + ": dst dist must be all zero (the rectified image is a pinhole)");
+    *a = lio::CamArg{};
+    a->fx = src->fx, a->fy = src->fy, a->cx = src->cx, a->cy = src->cy;
+    a->k1 = src->dist[0], a->k2 = src->dist[1], a->p1 = src->dist[2], a->p2 = src->dist[3];
+    a->k3 = src->dist[4], a->k4 = src->dist[5], a->k5 = src->dist[6], a->k6 = src->dist[7];
+    a->r2_max = std::numeric_limits<double>::infinity();
+    a->width = src->width, a->height = src->height;
+    *d = lio::UdDst{dst->fx, dst->fy, dst->cx, dst->cy, dst->width, dst->height};
+    return LIO_OK;
+}
+
+int lio_undistort_map(lio_filter* f, const lio_camera* src, const lio_camera* dst_opt, double* uv_opt, int32_t* sxy_opt,
+                      uint8_t* axy_opt) {
+    const char* what = "lio_undistort_map";
+    lio::CamArg a{};
+    lio::UdDst d{};
+    int rc = undistort_cams_arg(what, src, dst_opt, &a, &d);
+    if (rc) return rc;
+    if ((rc = denoise_handle(f, what))) return rc;
+    HIP_TRY(hipSetDevice(f->dev));
+    return status(lio::undistort_map(f->pj, a, d, uv_opt, sxy_opt, axy_opt, f->st), what);
+}
+
+struct lio_undistorter {
+    int dev = 0;
+    hipStream_t st = nullptr;
+    lio::UndistortBuf u;
+};
+
+int lio_undistorter_create(int device, lio_undistorter** out) {
+    if (!out) return fail(LIO_ERR_ARG, "lio_undistorter_create: out is NULL");
+    *out = nullptr;
+    int rc = check_device(device);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(device));
+    auto* h = new lio_undistorter();
+    h->dev = device;
+    if (hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking) != hipSuccess) {
+        delete h;
+        return fail(LIO_ERR_HIP, "hipStreamCreate failed");
+    }
+    if ((rc = lio::undistorter_init(h->u))) {
+        lio::undistorter_free(h->u);
+        (void)hipStreamDestroy(h->st);
+        delete h;
+        return status(rc, "lio_undistorter_create");
+    }
+    *out = h;
+    return LIO_OK;
+}
+
+int lio_undistorter_destroy(lio_undistorter* h) {
+    if (!h) return LIO_OK;
+    (void)hipSetDevice(h->dev);
+    (void)hipStreamSynchronize(h->st);
+    lio::undistorter_free(h->u);
+    (void)hipStreamDestroy(h->st);
+    delete h;
+    return LIO_OK;
+}
+
+// a NULL handle without a device is the missing device (lio_undistorter_create cannot have succeeded)
+static int undistorter_handle(lio_undistorter* h, const char* what) {
+    if (h) return LIO_OK;
+    const int rc = check_device(0);
+    if (rc) return rc;
+    return fail(LIO_ERR_ARG, std::string(what) + ": handle is NULL");
+}
+
+int lio_undistorter_set_camera(lio_undistorter* h, const lio_camera* src, const lio_camera* dst_opt, int channels,
+                               const uint8_t* border_opt) {
+    const char* what = "lio_undistorter_set_camera";
+    lio::CamArg a{};
+    lio::UdDst d{};
+    int rc = undistort_cams_arg(what, src, dst_opt, &a, &d);
+    if (rc) return rc;
+    if (channels != 1 && channels != 3) return fail(LIO_ERR_ARG, std::string(what) + ": channels must be 1 or 3");
+    if ((rc = undistorter_handle(h, what))) return rc;
+    const uint8_t black[3] = {0, 0, 0};
+    HIP_TRY(hipSetDevice(h->dev));
+    return status(lio::undistorter_set_camera(h->u, a, d, channels, border_opt ? border_opt : black, h->st), what);
+}
+
+int lio_undistorter_run(lio_undistorter* h, const uint8_t* image, int64_t pitch, uint8_t* out, int64_t out_pitch) {
+    const std::string what = "lio_undistorter_run";
+    if (!image) return fail(LIO_ERR_ARG, what + ": image is NULL");
+    if (!out) return fail(LIO_ERR_ARG, what + ": out is NULL");
+    const int rc = undistorter_handle(h, what.c_str());
+    if (rc) return rc;
+    if (!h->u.have_camera) return fail(LIO_ERR_STATE, what + ": no camera (call lio_undistorter_set_camera first)");
+    if (pitch < (int64_t)h->u.channels * h->u.sw)
+        return fail(LIO_ERR_ARG, what + ": pitch must be at least channels x width bytes of the raw image");
+    if (out_pitch < (int64_t)h->u.channels * h->u.dw)
+        return fail(LIO_ERR_ARG, what + ": out_pitch must be at least channels x width bytes of the rectified image");
+    HIP_TRY(hipSetDevice(h->dev));
+    return status(lio::undistorter_run(h->u, image, pitch, out, out_pitch, h->st), what.c_str());
+}
+
+int lio_undistorter_get_timing(lio_undistorter* h, double* ms3) {
+    const int rc = undistorter_handle(h, "lio_undistorter_get_timing");
+    if (rc) return rc;
+    if (!ms3) return fail(LIO_ERR_ARG, "lio_undistorter_get_timing: ms3 is NULL");
+    for (int k = 0; k < lio::kUdStages; ++k) ms3[k] = h->u.ms[k];
     return LIO_OK;
 }
 

@@ -18,10 +18,28 @@
 #include <algorithm>
 #include <cstring>
 
+#include "lio_camera_dev.hpp"
 #include "lio_colorize.hpp"
 #include "lio_scratch.hpp"
 
 namespace lio {
+
+// pinned host memory of at least `need` bytes, grown geometrically and counted
+int grow_pinned(uint8_t** p, size_t& bytes, size_t need) {
+    if (need <= bytes && *p) return kOk;
+    const size_t c = grown(need, bytes, (size_t)1 << 20);
+    if (*p) (void)hipHostFree(*p);
+    *p = nullptr;
+    bytes = 0;
+    count_alloc();
+    if (hipHostMalloc(reinterpret_cast<void**>(p), c, hipHostMallocDefault) != hipSuccess) {
+        *p = nullptr;
+        return kNoMem;
+    }
+    bytes = c;
+    return kOk;
+}
+
 namespace {
 
 struct Projected {
@@ -37,19 +55,13 @@ __device__ __forceinline__ Projected cz_project(const float* __restrict__ p, con
     const double yc = ((c.R[3] * x + c.R[4] * y) + c.R[5] * z) + c.t[1];
     const double zc = ((c.R[6] * x + c.R[7] * y) + c.R[8] * z) + c.t[2];
     const double xn = xc / zc, yn = yc / zc;
-    const double r2 = xn * xn + yn * yn;
-    const double num = 1.0 + ((c.k3 * r2 + c.k2) * r2 + c.k1) * r2;
-    const double den = 1.0 + ((c.k6 * r2 + c.k5) * r2 + c.k4) * r2;
-    const double rad = num / den;
-    const double a1 = (2.0 * xn) * yn, a2 = r2 + (2.0 * xn) * xn, a3 = r2 + (2.0 * yn) * yn;
-    const double xd = xn * rad + (c.p1 * a1 + c.p2 * a2);
-    const double yd = yn * rad + (c.p1 * a3 + c.p2 * a1);
+    const Distorted d = cam_distort(xn, yn, c);  // r2 ... u, v: shared with the undistortion map (lio_camera_dev.hpp)
     Projected o;
-    o.u = c.fx * xd + c.cx;
-    o.v = c.fy * yd + c.cy;
+    o.u = d.u;
+    o.v = d.v;
     o.zc = zc;
     // every comparison is false on NaN
-    o.valid = zc > 0.0 && r2 <= c.r2_max && o.u >= 0.0 && o.u < (double)c.width && o.v >= 0.0 && o.v < (double)c.height;
+    o.valid = zc > 0.0 && d.r2 <= c.r2_max && o.u >= 0.0 && o.u < (double)c.width && o.v >= 0.0 && o.v < (double)c.height;
     o.px = o.valid ? (int)o.u : -1;  // truncation only after the test: u = -0.5 is invalid, not pixel 0
     o.py = o.valid ? (int)o.v : -1;
     return o;
@@ -151,22 +163,6 @@ __global__ __launch_bounds__(256) void cz_resolve_kernel(const float* __restrict
         }
     }
     cz_count(replaced, count);
-}
-
-// pinned host memory of at least `need` bytes, grown geometrically and counted
-int grow_pinned(uint8_t** p, size_t& bytes, size_t need) {
-    if (need <= bytes && *p) return kOk;
-    const size_t c = grown(need, bytes, (size_t)1 << 20);
-    if (*p) (void)hipHostFree(*p);
-    *p = nullptr;
-    bytes = 0;
-    count_alloc();
-    if (hipHostMalloc(reinterpret_cast<void**>(p), c, hipHostMallocDefault) != hipSuccess) {
-        *p = nullptr;
-        return kNoMem;
-    }
-    bytes = c;
-    return kOk;
 }
 
 }  // namespace

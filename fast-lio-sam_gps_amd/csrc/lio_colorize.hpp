@@ -36,6 +36,10 @@ void project_free(ProjectBuf& b);
 int project_points(ProjectBuf& b, const float* d_pts, int64_t n, int stride, const CamArg& cam, double* uv_opt,
                    double* zc_opt, int32_t* pix_opt, uint8_t* valid, hipStream_t st);
 
+// pinned host memory of at least `need` bytes, grown geometrically and counted (lio_alloc_count): the image staging
+// of the colorizer and of the undistorter
+int grow_pinned(uint8_t** p, size_t& bytes, size_t need);
+
 // the state of a lio_colorizer: the cloud and the per-point state stay on the device between frames
 struct ColorizeBuf {
     float* pts = nullptr;  // n x stride

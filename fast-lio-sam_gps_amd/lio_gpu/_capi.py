@@ -59,6 +59,8 @@ EXPORTS = [
     "lio_abi_camera_struct_sizes", "lio_project_points", "lio_colorizer_create", "lio_colorizer_destroy",
     "lio_colorizer_set_params", "lio_colorizer_set_cloud", "lio_colorizer_add_frame", "lio_colorizer_get",
     "lio_colorizer_reset", "lio_colorizer_get_timing",
+    "lio_undistort_map", "lio_undistorter_create", "lio_undistorter_destroy", "lio_undistorter_set_camera",
+    "lio_undistorter_run", "lio_undistorter_get_timing",
 ]
 
 
@@ -257,6 +259,13 @@ def _declare(L):
         "lio_colorizer_get": (C.c_int, [vp, C.POINTER(C.c_uint8), C.POINTER(C.c_int32), dp]),
         "lio_colorizer_reset": (C.c_int, [vp]),
         "lio_colorizer_get_timing": (C.c_int, [vp, dp]),
+        "lio_undistort_map": (C.c_int, [vp, C.POINTER(Camera), C.POINTER(Camera), dp, C.POINTER(C.c_int32),
+                                        C.POINTER(C.c_uint8)]),
+        "lio_undistorter_create": (C.c_int, [C.c_int, C.POINTER(vp)]),
+        "lio_undistorter_destroy": (C.c_int, [vp]),
+        "lio_undistorter_set_camera": (C.c_int, [vp, C.POINTER(Camera), C.POINTER(Camera), C.c_int, C.POINTER(C.c_uint8)]),
+        "lio_undistorter_run": (C.c_int, [vp, vp, C.c_int64, vp, C.c_int64]),
+        "lio_undistorter_get_timing": (C.c_int, [vp, dp]),
         "lio_ctx_create": (C.c_int, [vp, C.POINTER(MatchParams), C.POINTER(vp)]),
         "lio_ctx_destroy": (C.c_int, [vp]),
         "lio_scan_set": (C.c_int, [vp, fp, C.c_int64]),

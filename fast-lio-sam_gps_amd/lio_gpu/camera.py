@@ -7,6 +7,9 @@ over the C-ABI.
 * :class:`Colorizer` — colours of a cloud from any number of frames, with an opt-in z-buffer (``lio_colorizer_*``)
 * :func:`pack_rgb` — PCL's packed ``rgb`` field; :func:`colorize_pcd` — ``colorize_pcd.py`` on files
 * :func:`world_to_camera` — the ``Rt`` of a keyframe from its pose and the LiDAR-to-camera extrinsic
+* :func:`undistort_map`, :class:`Undistorter`, :func:`undistort_image` — the scripts' ``cv2.undistort(img, K, D, None,
+  K)`` on every frame (post_process/undistort_image.py:21-27), as a 1/32-pixel map and an integer bilinear gather
+  (``lio_undistort_map``, ``lio_undistorter_*``); :meth:`CameraModel.rectified` is the camera of its output
 
 Images are numpy arrays (``height x width x 3`` uint8); decoding them is the caller's.  Every result follows the
 contract of include/lio_gpu.h bit for bit: IEEE double operations in a written order, nothing fused.
@@ -15,7 +18,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 
 import numpy as np
 
@@ -62,6 +65,12 @@ class CameraModel:
     def _c(self) -> _capi.Camera:
         return _capi.Camera(self.fx, self.fy, self.cx, self.cy, (C.c_double * 8)(*self.dist), self.r2_max, self.width,
                             self.height)
+
+    def rectified(self, **overrides) -> "CameraModel":
+        """The pinhole camera of this camera's undistorted image: the same intrinsics and size with zero distortion
+        (``overrides``: other ``fx fy cx cy width height``).  It is what :class:`Colorizer` takes for a rectified
+        image, and the ``new_camera`` of :func:`undistort_image`."""
+        return replace(self, **{"dist": (), **overrides})
 
 
 def _pose(Rt) -> np.ndarray:
@@ -127,6 +136,112 @@ def _image(image, camera: CameraModel):
     if a.strides[2] != 1 or a.strides[1] != 3 or a.strides[0] < 3 * camera.width:
         a = np.ascontiguousarray(a)
     return a, a.strides[0]
+
+
+def _plane(image, width: int, height: int, what: str = "image"):
+    """(array kept alive, row pitch in bytes, channels) of a height x width (x 1) or height x width x 3 uint8 image;
+    a view whose pixels are packed (rows may be padded) is passed as it is, anything else is copied"""
+    a = np.asarray(image)
+    if a.ndim == 3 and a.shape[2] == 1:
+        a = a[:, :, 0]
+    ch = 1 if a.ndim == 2 else 3
+    if a.dtype != np.uint8 or a.ndim not in (2, 3) or (a.ndim == 3 and a.shape[2] != 3):
+        raise ValueError(f"{what}: a height x width, height x width x 1 or height x width x 3 uint8 array is expected")
+    if a.shape[:2] != (height, width):
+        raise ValueError(f"{what}: shape {a.shape[:2]} is not the camera's (height, width) = {(height, width)}")
+    if a.strides[-1] != 1 or a.strides[1] != ch or a.strides[0] < ch * width:
+        a = np.ascontiguousarray(a)
+    return a, a.strides[0], ch
+
+
+def undistort_map(src: CameraModel, dst: CameraModel | None = None, handle: _Handle | None = None):
+    """The map of ``lio_undistort_map`` from the raw camera ``src`` to the rectified camera ``dst`` (none: ``src``'s
+    intrinsics and size): ``(uv, sxy, axy)``, each ``height x width x 2`` of ``dst``: the unquantised source
+    position (float64), its integer part (int32; ``INT32_MIN``: FAR) and its fraction in 1/32 pixel (uint8)."""
+    h = handle or _Handle()
+    d = dst or src
+    uv = np.zeros((d.height, d.width, 2), np.float64)
+    sxy = np.zeros((d.height, d.width, 2), np.int32)
+    axy = np.zeros((d.height, d.width, 2), np.uint8)
+    cs = src._c()
+    cd = dst._c() if dst is not None else None
+    check(lib().lio_undistort_map(h._h, C.byref(cs), C.byref(cd) if cd is not None else None, uv.ctypes.data_as(_dp),
+                                  sxy.ctypes.data_as(C.POINTER(C.c_int32)), axy.ctypes.data_as(C.POINTER(C.c_uint8))))
+    return uv, sxy, axy
+
+
+class Undistorter:
+    """``cv2.undistort(img, K, D, None, K)`` per frame: ``set_camera`` once (the map stays on the device), then call
+    the handle on every image.  Bilinear in 1/32 pixel with a constant ``border`` per tap, by the contract of
+    include/lio_gpu.h (agreement with OpenCV is a reading of its source, not a test)."""
+
+    def __init__(self, device: int = 0):
+        self._h = C.c_void_p()
+        self._shape = None  # (src height, src width, dst height, dst width, channels)
+        check(lib().lio_undistorter_create(device, C.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            lib().lio_undistorter_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_camera(self, camera: CameraModel, new_camera: CameraModel | None = None, channels: int = 3, border=(0, 0, 0)):
+        """``camera``: the raw image's; ``new_camera``: the rectified image's pinhole (none: ``camera.rectified()``, the
+        scripts' call); ``border``: one value, or one per channel"""
+        b = np.zeros(3, np.uint8)
+        b[:] = np.asarray(border, np.uint8).ravel()[:3] if np.ndim(border) else np.uint8(border)
+        cs = camera._c()
+        cd = new_camera._c() if new_camera is not None else None
+        self._shape = None
+        check(lib().lio_undistorter_set_camera(self._h, C.byref(cs), C.byref(cd) if cd is not None else None, int(channels),
+                                               b.ctypes.data_as(C.POINTER(C.c_uint8))))
+        d = new_camera or camera
+        self._shape = (camera.height, camera.width, d.height, d.width, int(channels))
+
+    def __call__(self, image, out=None) -> np.ndarray:
+        """the rectified image, in the shape of the input (``h x w`` stays two-dimensional).  ``out``: a uint8 array
+        of that shape to write into (its rows may be padded; the padding is not touched)."""
+        if self._shape is None:  # the library's state error, with its message
+            img = np.zeros(1, np.uint8)
+            check(lib().lio_undistorter_run(self._h, img.ctypes.data_as(C.c_void_p), 0, img.ctypes.data_as(C.c_void_p), 0))
+        sh, sw, dh, dw, ch = self._shape
+        img, pitch, c = _plane(image, sw, sh)
+        if c != ch:
+            raise ValueError(f"image: {c} channel(s), the handle was set up for {ch}")
+        shape = (dh, dw) if np.ndim(image) == 2 else (dh, dw, ch)
+        if out is None:
+            out = np.empty(shape, np.uint8)
+        if not isinstance(out, np.ndarray) or out.dtype != np.uint8 or out.shape != shape or not out.flags.writeable:
+            raise ValueError(f"out: a writeable uint8 array of shape {shape} is expected")
+        o = out[:, :, 0] if (out.ndim == 3 and ch == 1) else out
+        if o.strides[-1] != 1 or o.strides[1] != ch or o.strides[0] < ch * dw:
+            raise ValueError("out: the pixels of a row must be packed (rows may be padded)")
+        check(lib().lio_undistorter_run(self._h, img.ctypes.data_as(C.c_void_p), pitch, o.ctypes.data_as(C.c_void_p),
+                                        o.strides[0]))
+        return out
+
+    def timing(self) -> dict:
+        """device ms of the last frame: upload (staging copy included), kernel, download"""
+        ms = np.zeros(3, np.float64)
+        check(lib().lio_undistorter_get_timing(self._h, ms.ctypes.data_as(_dp)))
+        return dict(zip(("upload_ms", "kernel_ms", "download_ms"), (float(v) for v in ms)))
+
+
+def undistort_image(image, camera: CameraModel, new_camera: CameraModel | None = None, border=(0, 0, 0)) -> np.ndarray:
+    """one image through a fresh :class:`Undistorter` (for many frames of one camera keep the handle)"""
+    a = np.asarray(image)
+    ud = Undistorter()
+    try:
+        ud.set_camera(camera, new_camera, channels=3 if (a.ndim == 3 and a.shape[2] == 3) else 1, border=border)
+        return ud(a)
+    finally:
+        ud.close()
 
 
 class Colorizer:

@@ -803,6 +803,58 @@ int lio_colorizer_reset(lio_colorizer* h);
  * resolve (without occlusion: 0, 0 and the fused kernel)                                                          */
 int lio_colorizer_get_timing(lio_colorizer* h, double* ms4);
 
+/* ------------------------------------------------------------- image undistortion (rectification; camera leg) */
+/* The image operation the reference's camera scripts run on every frame before anything reads it:
+ * cv2.undistort(img, K, D, None, K) (post_process/undistort_image.py:21-27, decompress_undistort_images.py:28,
+ * extract_pointcloud_image.py:26-28, extraction.py:21-22).  The contract is the library's own, exact to the bit.
+ *   cameras   src: the raw image's lio_camera (intrinsics, dist, width, height).  dst_opt: the rectified image's
+ *             fx fy cx cy width height; NULL means src's values, which is the scripts' call; its dist must be all
+ *             zero.  r2_max of both is ignored (OpenCV has no such bound here).  Widths and heights of both are in
+ *             1..32767 (OpenCV's short map range; a map record packs into 8 bytes).
+ *   map       for the output pixel in column j and row i, in IEEE double, nothing fused, in this order:
+ *               xn = ((double)j - dst.cx) / dst.fx;  yn = ((double)i - dst.cy) / dst.fy;
+ *             then exactly the lines of lio_project_points from r2 = xn xn + yn yn through u = fx xd + cx;
+ *             v = fy yd + cy with src's coefficients (one device function serves both entries).
+ *   quantise  OpenCV's CV_16SC2 fixed-point map with INTER_BITS = 5: qu = rint(u * 32.0), qv = rint(v * 32.0), TIES
+ *             TO EVEN.  If !(fabs(qu) < 2^30 && fabs(qv) < 2^30) (THE TEST IS FALSE ON NaN) the pixel is FAR: sx = sy
+ *             = INT32_MIN, ax = ay = 0.  Otherwise, with qu and qv taken as int: sx = qu >> 5 (arithmetic shift:
+ *             floor), ax = qu & 31; sy, ay likewise.
+ *   sample    INTER_LINEAR with BORDER_CONSTANT per tap: the taps (sx, sy) (sx + 1, sy) (sx, sy + 1) (sx + 1, sy + 1)
+ *             have the integer weights (32 - ax)(32 - ay), ax (32 - ay), (32 - ax) ay, ax ay.  A tap outside 0 <= x
+ *             < src.width, 0 <= y < src.height contributes the border value of its channel and is NEVER LOADED, even
+ *             when its weight is 0 (the last column of an identity map has sx + 1 == width).  Per channel
+ *             out = (sum w p + 512) >> 10.  A FAR pixel is the border value.
+ * As far as we read OpenCV's source this is its remap: the 32 x 32 bilinear table entries (32 - a)(32 - b) / 1024
+ * are exact in float, scaled by 2^15 they are integers that sum to 32768 (its sum correction never fires), and
+ * (sum 32 w p + 2^14) >> 15 equals the line above.  AGREEMENT WITH cv2.undistort IS THIS READING OF ITS SOURCE AND IS
+ * UNVERIFIED: OpenCV was not available where this was written, and its own map arithmetic before the 1/32-pixel
+ * rounding (SIMD, incremental row terms) depends on its version and is not reproduced.
+ * images: uint8, channels 1 or 3, the channel order is irrelevant.  Input: src.height rows of `pitch` bytes;
+ * output: dst.height rows of `out_pitch` bytes.  Only channels x width bytes of a row are read or written: the
+ * output's padding bytes are left untouched.  border_opt: 3 uint8 (one per channel); NULL means 0 0 0, the scripts'
+ * default.
+ *
+ * lio_undistort_map: the map alone, dst.height x dst.width x 2 values each, row-major (any may be NULL): uv, the
+ * unquantised u, v; sxy: sx, sy; axy: ax, ay.
+ * lio_undistorter: set_camera computes the packed map and keeps it on the device; run uploads a frame, gathers
+ * and downloads through staging that is reused across frames.  get_timing: device ms of the last run from stream
+ * events: upload (its staging copy included), kernel, download (the device-to-host copy; the rows then go to
+ * `out` on the host).
+ * LIO_ERR_ARG before any device work, with a message that names the bound: a NULL src, image, out or ms3, a width
+ * or height outside 1..32767, a non-finite intrinsic or coefficient, dst fx or fy equal to 0, a non-zero dst dist,
+ * channels not 1 or 3, pitch < channels x src.width, out_pitch < channels x dst.width.  The checks that need no
+ * handle are made before the handle is looked at.  LIO_ERR_STATE: run before set_camera.  From the second run of
+ * one size on nothing is allocated (lio_alloc_count); repeated runs give identical bits.                        */
+int lio_undistort_map(lio_filter* f, const lio_camera* src, const lio_camera* dst_opt, double* uv_opt, int32_t* sxy_opt,
+                      uint8_t* axy_opt);
+typedef struct lio_undistorter lio_undistorter;
+int lio_undistorter_create(int device, lio_undistorter** out);
+int lio_undistorter_destroy(lio_undistorter* h);
+int lio_undistorter_set_camera(lio_undistorter* h, const lio_camera* src, const lio_camera* dst_opt, int channels,
+                               const uint8_t* border_opt);
+int lio_undistorter_run(lio_undistorter* h, const uint8_t* image, int64_t pitch, uint8_t* out, int64_t out_pitch);
+int lio_undistorter_get_timing(lio_undistorter* h, double* ms3);
+
 /* ------------------------------------------- wire / disk formats (§8(f) row 4) */
 /* One output column of a packed point record: byte offset, sensor_msgs/PointField datatype
  * (INT8 1, UINT8 2, INT16 3, UINT16 4, INT32 5, UINT32 6, FLOAT32 7, FLOAT64 8; 0 = absent -> 0)

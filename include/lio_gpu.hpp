@@ -876,6 +876,65 @@ private:
     size_t n_ = 0;
 };
 
+// the map of lio_undistort_map, dst.height x dst.width x 2 each: u, v; sx, sy (INT32_MIN: FAR); ax, ay
+struct UndistortMap {
+    std::vector<double> uv;
+    std::vector<int32_t> sxy;
+    std::vector<uint8_t> axy;
+};
+
+// The 1/32-pixel map from the raw camera `src` to the rectified pinhole `dst` (none: src's intrinsics and size) by
+// the contract of lio_undistort_map.
+inline void undistort_map(FilterGPU& f, const CameraModel& src, const CameraModel* dst, UndistortMap& out) {
+    const CameraModel& d = dst ? *dst : src;
+    const size_t n = 2 * (size_t)std::max(d.width, 0) * (size_t)std::max(d.height, 0);
+    out.uv.assign(n, 0.0);
+    out.sxy.assign(n, 0);
+    out.axy.assign(n, 0);
+    const lio_camera cs = src.c();
+    lio_camera cd{};
+    if (dst) cd = dst->c();
+    check(lio_undistort_map(f.handle(), &cs, dst ? &cd : nullptr, out.uv.data(), out.sxy.data(), out.axy.data()),
+          "undistort_map");
+}
+
+// cv2.undistort(img, K, D, None, K) per frame (lio_undistorter), as the camera scripts call it on every image
+// (post_process/undistort_image.py:21-27): setCamera once — the map stays on the device — then undistort per frame.
+class Undistorter {
+public:
+    explicit Undistorter(int device = 0) { check(lio_undistorter_create(device, &h_), "lio_undistorter_create"); }
+    ~Undistorter() { lio_undistorter_destroy(h_); }
+    Undistorter(const Undistorter&) = delete;
+    Undistorter& operator=(const Undistorter&) = delete;
+    // dst: the rectified image's pinhole (none: src's intrinsics and size, the scripts' call); channels 1 or 3;
+    // border: one value per channel
+    void setCamera(const CameraModel& src, const CameraModel* dst = nullptr, int channels = 3,
+                   const std::array<uint8_t, 3>& border = {0, 0, 0}) {
+        const lio_camera cs = src.c();
+        lio_camera cd{};
+        if (dst) cd = dst->c();
+        check(lio_undistorter_set_camera(h_, &cs, dst ? &cd : nullptr, channels, border.data()), "Undistorter::setCamera");
+        sw_ = src.width, dw_ = dst ? dst->width : src.width, channels_ = channels;
+    }
+    // image: the raw frame, rows of `pitch` bytes (0: channels * width); out: the rectified frame, rows of
+    // `out_pitch` bytes (0 likewise), of which channels * width are written
+    void undistort(const uint8_t* image, uint8_t* out, int64_t pitch = 0, int64_t out_pitch = 0) {
+        check(lio_undistorter_run(h_, image, pitch ? pitch : (int64_t)channels_ * sw_, out,
+                                  out_pitch ? out_pitch : (int64_t)channels_ * dw_),
+              "Undistorter::undistort");
+    }
+    // device ms of the last frame: upload, kernel, download
+    std::array<double, 3> timing() {
+        std::array<double, 3> ms{};
+        check(lio_undistorter_get_timing(h_, ms.data()), "Undistorter::timing");
+        return ms;
+    }
+
+private:
+    lio_undistorter* h_ = nullptr;
+    int sw_ = 0, dw_ = 0, channels_ = 3;
+};
+
 // Open3D's PointCloud::SegmentPlane as the offline pipeline calls it (post_process/clustering.py:21-28), in the
 // shape of pcl::SACSegmentation: setInputCloud / setDistanceThreshold / setMaxIterations / setSeed / segment.
 // Every hypothesis is evaluated; the winner minimises (-inliers, fixed-point squared error, hypothesis index)
