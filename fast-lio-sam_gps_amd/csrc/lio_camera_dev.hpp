@@ -4,7 +4,9 @@
 // (lio_undistort.hip) on an output pixel's, so a ray has the same u, v bits in both.  Files that include this
 // are compiled with -ffp-contract=off: no multiply-add is fused.
 #pragma once
-#include "lio_colorize.hpp"
+#include <hip/hip_runtime.h>
+
+#include "lio_camera.hpp"
 
 namespace lio {
 

@@ -2,10 +2,9 @@
 // buffers, and the host drivers (IESKF update, PCL-semantics ICP loop).
 // There is deliberately no CPU compute path: every compute entry point runs
 // the gfx950 kernels or fails with LIO_ERR_NODEV / LIO_ERR_HIP.
-#include "../../include/lio_gpu.h"
-
-#include <hip/hip_runtime.h>
-
+// This file: map, ctx, match, IESKF, the filter handle with voxel grid, submap voxelize and scan preprocessing,
+// cloud2 / PCD and timing.  The offline leg on a lio_filter is in lio_capi_post.cpp, the camera leg in
+// lio_capi_camera.cpp; what all three share is lio_capi_util.hpp.
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -18,63 +17,13 @@
 #include <vector>
 
 #include "ieskf.hpp"
-#include "lio_error.hpp"
-#include "lio_kernels.hpp"
-#include "lio_filter.hpp"
-#include "lio_denoise.hpp"
-#include "lio_cluster.hpp"
-#include "lio_dbscan.hpp"
-#include "lio_colorize.hpp"
-#include "lio_undistort.hpp"
-#include "lio_gpsalign.hpp"
-#include "lio_plane.hpp"
+#include "lio_capi_util.hpp"
 #include "lio_pool.hpp"
 #include "lio_mapupd.hpp"
-#include "lio_scratch.hpp"
+
+using namespace lio::capi;
 
 namespace {
-
-int fail(int code, const std::string& msg) {
-    lio::last_error() = msg;
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                           \
-    do {                                                                                        \
-        hipError_t e_ = (expr);                                                                 \
-        if (e_ != hipSuccess) return fail(LIO_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-int check_device(int dev) {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
-        return fail(LIO_ERR_NODEV, "no HIP device visible (this library has no CPU path)");
-    if (dev < 0 || dev >= n) return fail(LIO_ERR_ARG, "device ordinal out of range");
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return fail(LIO_ERR_HIP, "hipGetDeviceProperties failed");
-    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        return fail(LIO_ERR_NODEV, std::string("built for gfx950, device is ") + prop.gcnArchName);
-    return LIO_OK;
-}
-
-static_assert(lio::kOk == LIO_OK && lio::kArg == LIO_ERR_ARG && lio::kHip == LIO_ERR_HIP && lio::kNoMem == LIO_ERR_NOMEM,
-              "the internal status codes are the public ones");
-
-// The public code and message of an internal driver's status.  arg_what: the call's wording of kArg.  Every kHip
-// has just left the failed HIP call's text in last_error() (LIO_HIP), taken here before fail() replaces it.
-int status(int rc, const char* what, const char* arg_what = "bad arguments") {
-    if (rc == lio::kOk) return LIO_OK;
-    if (rc == lio::kNoMem) return fail(LIO_ERR_NOMEM, std::string(what) + ": out of device memory");
-    if (rc == lio::kArg) return fail(LIO_ERR_ARG, std::string(what) + ": " + arg_what);
-    const std::string detail = lio::last_error();
-    return fail(LIO_ERR_HIP, std::string(what) + " failed (" + detail + ")");
-}
-
-template <class T>
-int grow(T** p, int64_t& cap, int64_t need, size_t elems_per = 1) {
-    if (lio::grow_buf(p, cap, need, elems_per)) return fail(LIO_ERR_NOMEM, "hipMalloc failed");
-    return LIO_OK;
-}
 
 struct EventPair {
     hipEvent_t a = nullptr, b = nullptr;
@@ -1067,29 +1016,8 @@ int lio_ieskf_update(lio_ctx* c, lio_state* xs, double* P, const lio_ieskf_param
 }
 
 // =============================================================================
-// filters
+// filters (struct lio_filter: lio_capi_util.hpp)
 // =============================================================================
-struct lio_filter {
-    int dev = 0;
-    hipStream_t st = nullptr;
-    lio::FilterBuf b;
-    float* d_in = nullptr;
-    int64_t in_cap = 0;
-    float* d_out = nullptr;
-    int64_t out_cap = 0;
-    int64_t* d_seg = nullptr;
-    int64_t seg_cap = 0;
-    double* d_T = nullptr;
-    int64_t T_cap = 0;
-    lio::ImuPose* d_poses = nullptr;
-    int64_t poses_cap = 0;
-    lio::DenoiseBuf dn;  // lio_sor_filter / lio_radius_first_seed / lio_denoise_slam_map
-    lio::ClusterBuf cl;  // lio_euclidean_clusters, lio_dbscan (with dn: the grid, the sorts and the scan)
-    lio::PlaneBuf pl;    // lio_segment_plane (with dn: the flags and the scan)
-    lio::GpsAlignBuf ga; // lio_gps_align, lio_similarity2d_fit, lio_georeference_xy
-    lio::ProjectBuf pj;  // lio_project_points, lio_undistort_map
-};
-
 static lio::UndistortEnd undistort_end(const lio_pose* e) {
     lio::UndistortEnd u{};
     if (!e) {
@@ -1109,6 +1037,12 @@ static lio::UndistortEnd undistort_end(const lio_pose* e) {
 
 static_assert(sizeof(lio_imu_pose) == sizeof(lio::ImuPose), "lio_imu_pose layout");
 
+// the filter's pinned staging buffer holds `need` bytes: max(need, 1.5 x old), no floor
+static int reserve_stage(lio::FilterBuf& b, size_t need) {
+    if (lio::grow_pinned(&b.h_stage, b.stage_bytes, need, 0)) return fail(LIO_ERR_NOMEM, "sweep staging: hipHostMalloc failed");
+    return LIO_OK;
+}
+
 // The host half of a sweep upload: rows i % every == 0 — Preprocess's point_filter_num drops the others
 // by index alone, so they never cross PCIe — and the IMU poses packed into the filter's pinned staging
 // buffer, for one DMA each (pageable sources would be staged by the runtime anyway).  *u = rows staged;
@@ -1119,17 +1053,7 @@ static int stage_sweep(lio::FilterBuf& b, const void* rows, int64_t n, size_t ro
     *u = (n + every - 1) / every;
     *pose_off = ((size_t)*u * row_bytes + 255) & ~(size_t)255;
     const size_t need = *pose_off + (size_t)np * sizeof(lio_imu_pose);
-    if (need > b.stage_bytes || !b.h_stage) {
-        if (b.h_stage) (void)hipHostFree(b.h_stage);
-        b.h_stage = nullptr;
-        const size_t c = std::max(need, b.stage_bytes + b.stage_bytes / 2);
-        lio::count_alloc();
-        if (hipHostMalloc(&b.h_stage, c) != hipSuccess) {
-            b.stage_bytes = 0;
-            return fail(LIO_ERR_NOMEM, "sweep staging: hipHostMalloc failed");
-        }
-        b.stage_bytes = c;
-    }
+    if (int rc = reserve_stage(b, need)) return rc;
     auto* dst = static_cast<uint8_t*>(b.h_stage);
     const auto* src = static_cast<const uint8_t*>(rows);
     if (every == 1) {
@@ -1198,17 +1122,7 @@ static int stage_sweep_select(lio::FilterBuf& b, const float* raw, int64_t n, in
     const int64_t ub = (n + every - 1) / every;  // candidate rows (i % every == 0)
     *pose_off = ((size_t)ub * stride * sizeof(float) + 255) & ~(size_t)255;
     const size_t need = *pose_off + (size_t)np * sizeof(lio_imu_pose);
-    if (need > b.stage_bytes || !b.h_stage) {
-        if (b.h_stage) (void)hipHostFree(b.h_stage);
-        b.h_stage = nullptr;
-        const size_t c = std::max(need, b.stage_bytes + b.stage_bytes / 2);
-        lio::count_alloc();
-        if (hipHostMalloc(&b.h_stage, c) != hipSuccess) {
-            b.stage_bytes = 0;
-            return fail(LIO_ERR_NOMEM, "sweep staging: hipHostMalloc failed");
-        }
-        b.stage_bytes = c;
-    }
+    if (int rc = reserve_stage(b, need)) return rc;
     const float blind2 = p->blind * p->blind;
     auto* d = static_cast<float*>(b.h_stage);
     const int pieces = ub >= 16384 ? std::min(kStageChunks, lio::HostPool::get().threads()) : 1;
@@ -1270,45 +1184,18 @@ static int upload_staged(const lio::FilterBuf& b, const StagePlan& plan, size_t 
     return LIO_OK;
 }
 
-int lio_filter_create(int device, lio_filter** out) {
-    if (!out) return fail(LIO_ERR_ARG, "out is NULL");
-    *out = nullptr;
-    int rc = check_device(device);
-    if (rc) return rc;
-    HIP_TRY(hipSetDevice(device));
-    auto* f = new lio_filter();
-    f->dev = device;
-    if (hipStreamCreateWithFlags(&f->st, hipStreamNonBlocking) != hipSuccess) {
-        delete f;
-        return fail(LIO_ERR_HIP, "hipStreamCreate failed");
-    }
-    *out = f;
-    return LIO_OK;
-}
+int lio_filter_create(int device, lio_filter** out) { return open_handle(device, out, "out is NULL"); }
 
 int lio_filter_destroy(lio_filter* f) {
-    if (!f) return LIO_OK;
-    (void)hipSetDevice(f->dev);
-    (void)hipStreamSynchronize(f->st);
-    lio::filter_free(f->b);
-    lio::denoise_free(f->dn);
-    lio::cluster_free(f->cl);
-    lio::plane_free(f->pl);
-    lio::gps_align_free(f->ga);
-    lio::project_free(f->pj);
-    for (void* q : {(void*)f->d_in, (void*)f->d_out, (void*)f->d_seg, (void*)f->d_T, (void*)f->d_poses})
-        if (q) (void)hipFree(q);
-    (void)hipStreamDestroy(f->st);
-    delete f;
-    return LIO_OK;
-}
-
-// the upload the filter entries open with: `floats` floats at `host` into f->d_in, grown to hold them
-static int upload_in(lio_filter* f, const float* host, int64_t floats) {
-    const int rc = grow(&f->d_in, f->in_cap, floats);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(f->d_in, host, (size_t)floats * sizeof(float), hipMemcpyHostToDevice, f->st));
-    return LIO_OK;
+    return close_handle(f, [](lio_filter& h) {
+        lio::filter_free(h.b);
+        lio::denoise_free(h.dn);
+        lio::cluster_free(h.cl);
+        lio::plane_free(h.pl);
+        lio::gps_align_free(h.ga);
+        lio::project_free(h.pj);
+        lio::dev_free(&h.d_in, &h.d_out, &h.d_seg, &h.d_T, &h.d_poses);
+    });
 }
 
 int lio_voxel_grid(lio_filter* f, const float* pts, int64_t n, int stride, const float leaf[3], float* out,
@@ -1325,585 +1212,7 @@ int lio_voxel_grid(lio_filter* f, const float* pts, int64_t n, int stride, const
     int64_t m = 0;
     rc = lio::voxel_grid(f->b, f->d_in, n, stride, leaf, f->d_out, &m, f->st);
     if (rc) return status(rc, "lio_voxel_grid");
-    if (m) HIP_TRY(hipMemcpyAsync(out, f->d_out, (size_t)m * stride * sizeof(float), hipMemcpyDeviceToHost, f->st));
-    HIP_TRY(hipStreamSynchronize(f->st));
-    *n_out = m;
-    return LIO_OK;
-}
-
-// ---- statistical outlier removal, first-seed radius query, intensity map denoise (lio_denoise.hip) ----
-// a NULL handle without a device is the missing device (lio_filter_create cannot have succeeded), not a bad argument
-static int denoise_handle(lio_filter* f, const char* what) {
-    if (f) return LIO_OK;
-    const int rc = check_device(0);
-    if (rc) return rc;
-    return fail(LIO_ERR_ARG, std::string(what) + ": handle is NULL");
-}
-
-int lio_sor_filter(lio_filter* f, const float* pts, int64_t n, int stride, int mean_k, double stddev_mul, int negative,
-                   float* out, int64_t* n_out, float* distances_opt, double* stats4_opt) {
-    int rc = denoise_handle(f, "lio_sor_filter");
-    if (rc) return rc;
-    if (!n_out || n < 0 || (n > 0 && (!pts || !out)) || stride < 3 || stride > lio::kMaxFields || mean_k < 1 ||
-        mean_k > 255 || n >= (int64_t)1 << 30)
-        return fail(LIO_ERR_ARG, "lio_sor_filter: bad arguments");
-    *n_out = 0;
-    HIP_TRY(hipSetDevice(f->dev));
-    if (n > 0) {
-        rc = grow(&f->d_out, f->out_cap, n * stride);
-        if (!rc) rc = upload_in(f, pts, n * stride);
-        if (rc) return rc;
-    }
-    int64_t m = 0;
-    rc = lio::sor_filter(f->dn, f->d_in, n, stride, mean_k, stddev_mul, negative != 0, f->d_out, &m, distances_opt,
-                         stats4_opt, f->st);
-    if (rc) return status(rc, "lio_sor_filter");
-    if (m) HIP_TRY(hipMemcpyAsync(out, f->d_out, (size_t)m * stride * sizeof(float), hipMemcpyDeviceToHost, f->st));
-    HIP_TRY(hipStreamSynchronize(f->st));
-    *n_out = m;
-    return LIO_OK;
-}
-
-int lio_radius_first_seed(lio_filter* f, const float* pts, int64_t n, int stride, const float* seeds_xyz, int64_t ns,
-                          float radius, int32_t* seed_out, float* d2_out_opt) {
-    int rc = denoise_handle(f, "lio_radius_first_seed");
-    if (rc) return rc;
-    if (n < 0 || ns < 0 || (n > 0 && (!pts || !seed_out)) || (ns > 0 && !seeds_xyz) || stride < 3 ||
-        stride > lio::kMaxFields || !(radius >= 0.f) || !std::isfinite(radius) || n >= (int64_t)1 << 30 ||
-        ns >= (int64_t)1 << 30)
-        return fail(LIO_ERR_ARG, "lio_radius_first_seed: bad arguments");
-    if (n == 0) return LIO_OK;
-    HIP_TRY(hipSetDevice(f->dev));
-    rc = lio::denoise_reserve(f->dn, std::max(n, ns));
-    if (rc) return status(rc, "lio_radius_first_seed");
-    if ((rc = upload_in(f, pts, n * stride))) return rc;
-    if (ns) HIP_TRY(hipMemcpyAsync(f->dn.seeds_xyz, seeds_xyz, (size_t)ns * 3 * sizeof(float), hipMemcpyHostToDevice, f->st));
-    rc = lio::radius_first_seed(f->dn, f->d_in, n, stride, f->dn.seeds_xyz, ns, radius, f->dn.seed_id, f->dn.seed_d2,
-                                f->st);
-    if (rc) return status(rc, "lio_radius_first_seed");
-    HIP_TRY(hipMemcpyAsync(seed_out, f->dn.seed_id, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, f->st));
-    if (d2_out_opt)
-        HIP_TRY(hipMemcpyAsync(d2_out_opt, f->dn.seed_d2, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, f->st));
-    HIP_TRY(hipStreamSynchronize(f->st));
-    return LIO_OK;
-}
-
-int lio_denoise_slam_map(lio_filter* f, const float* pts, int64_t n, const lio_denoise_params* p, float* out,
-                         int64_t* n_out, int64_t* counts5_opt) {
-    int rc = denoise_handle(f, "lio_denoise_slam_map");
-    if (rc) return rc;
-    if (!p || !n_out || n < 0 || (n > 0 && (!pts || !out)) || p->mean_k < 1 || p->mean_k > 255 ||
-        !(p->cluster_seed_radius >= 0.f) || !(p->denoise_radius >= 0.f) || !std::isfinite(p->cluster_seed_radius) ||
-        !std::isfinite(p->denoise_radius) || n >= (int64_t)1 << 29)
-        return fail(LIO_ERR_ARG, "lio_denoise_slam_map: bad arguments");
-    *n_out = 0;
-    if (counts5_opt)
-        for (int k = 0; k < 5; ++k) counts5_opt[k] = 0;
-    if (n == 0) return LIO_OK;
-    HIP_TRY(hipSetDevice(f->dev));
-    rc = grow(&f->d_out, f->out_cap, n * 4);
-    if (!rc) rc = upload_in(f, pts, n * 4);
-    if (rc) return rc;
-    const lio::DenoiseParams dp{p->seed_thres,  p->cluster_seed_radius, p->denoise_radius,
-                                p->noise_thres, p->mean_k,              p->stddev_mul};
-    int64_t m = 0;
-    rc = lio::denoise_slam_map(f->dn, f->d_in, n, dp, f->d_out, &m, counts5_opt, f->st);
-    if (rc) return status(rc, "lio_denoise_slam_map");
-    if (m) HIP_TRY(hipMemcpyAsync(out, f->d_out, (size_t)m * 4 * sizeof(float), hipMemcpyDeviceToHost, f->st));
-    HIP_TRY(hipStreamSynchronize(f->st));
-    *n_out = m;
-    return LIO_OK;
-}
-
-// ---- Euclidean cluster extraction and DBSCAN, both with per-cluster bounding boxes (lio_cluster.hip, lio_dbscan.hip) ----
-// what both entries open with: the argument check (r: tolerance / eps; least: min_size / min_samples), the
-// outputs of a call that finds nothing, the device and the upload.  The caller is done when this fails or n == 0.
-static int cluster_begin(lio_filter* f, const char* what, const float* pts, int64_t n, int stride, float r, int64_t least,
-                         const int32_t* labels_out, int64_t* n_clusters, int64_t cap_clusters, int64_t* offsets_opt,
-                         int64_t* stats4_opt) {
-    const int rc = denoise_handle(f, what);
-    if (rc) return rc;
-    if (!n_clusters || n < 0 || n >= (int64_t)1 << 31 || (n > 0 && (!pts || !labels_out)) || stride < 3 ||
-        stride > lio::kMaxFields || !(r > 0.f) || !std::isfinite(r) || least < 1 || cap_clusters < 0)
-        return fail(LIO_ERR_ARG, std::string(what) + ": bad arguments");
-    *n_clusters = 0;
-    if (stats4_opt)
-        for (int k = 0; k < 4; ++k) stats4_opt[k] = 0;
-    if (offsets_opt) offsets_opt[0] = 0;
-    if (n == 0) return LIO_OK;
-    HIP_TRY(hipSetDevice(f->dev));
-    return upload_in(f, pts, n * stride);
-}
-
-// what both entries end with: labels, DBSCAN's core flags, the grouped indices, offsets and boxes of the first
-// min(clusters, cap_clusters) clusters, the wait, and the counts (stats[2] = clusters, stats[3] = points in them)
-static int cluster_download(lio_filter* f, int64_t n, const int64_t (&stats)[4], int32_t* labels_out, uint8_t* core_opt,
-                            int64_t* n_clusters, int64_t cap_clusters, int64_t* offsets_opt, int32_t* indices_opt,
-                            float* aabb6_opt, int64_t* stats4_opt) {
-    const int64_t m = std::min(stats[2], cap_clusters);
-    HIP_TRY(hipMemcpyAsync(labels_out, f->cl.labels, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, f->st));
-    if (core_opt) HIP_TRY(hipMemcpyAsync(core_opt, f->cl.rank_of, (size_t)n, hipMemcpyDeviceToHost, f->st));
-    if (indices_opt && stats[3])
-        HIP_TRY(hipMemcpyAsync(indices_opt, f->cl.indices, (size_t)stats[3] * sizeof(int32_t), hipMemcpyDeviceToHost, f->st));
-    if (offsets_opt)
-        HIP_TRY(hipMemcpyAsync(offsets_opt, f->cl.offsets, (size_t)(m + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, f->st));
-    if (aabb6_opt && m)
-        HIP_TRY(hipMemcpyAsync(aabb6_opt, f->cl.aabb, (size_t)m * 6 * sizeof(float), hipMemcpyDeviceToHost, f->st));
-    HIP_TRY(hipStreamSynchronize(f->st));
-    *n_clusters = stats[2];
-    if (stats4_opt)
-        for (int k = 0; k < 4; ++k) stats4_opt[k] = stats[k];
-    return LIO_OK;
-}
-
-int lio_euclidean_clusters(lio_filter* f, const float* pts, int64_t n, int stride, float tolerance, int64_t min_size,
-                           int64_t max_size, int32_t* labels_out, int64_t* n_clusters, int64_t cap_clusters,
-                           int64_t* offsets_opt, int32_t* indices_opt, float* aabb6_opt, int64_t* stats4_opt) {
-    int rc = cluster_begin(f, "lio_euclidean_clusters", pts, n, stride, tolerance, min_size, labels_out, n_clusters,
-                           cap_clusters, offsets_opt, stats4_opt);
-    if (rc || n == 0) return rc;
-    lio::ClusterCounts cc;
-    rc = lio::euclidean_clusters(f->dn, f->cl, f->d_in, n, stride, tolerance, min_size, max_size, cap_clusters, &cc, f->st);
-    if (rc) return status(rc, "lio_euclidean_clusters");
-    return cluster_download(f, n, {cc.finite, cc.components, cc.clusters, cc.clustered_points}, labels_out, nullptr,
-                            n_clusters, cap_clusters, offsets_opt, indices_opt, aabb6_opt, stats4_opt);
-}
-
-int lio_dbscan(lio_filter* f, const float* pts, int64_t n, int stride, float eps, int64_t min_samples,
-               int32_t* labels_out, uint8_t* core_opt, int64_t* n_clusters, int64_t cap_clusters,
-               int64_t* offsets_opt, int32_t* indices_opt, float* aabb6_opt, int64_t* stats4_opt) {
-    int rc = cluster_begin(f, "lio_dbscan", pts, n, stride, eps, min_samples, labels_out, n_clusters, cap_clusters,
-                           offsets_opt, stats4_opt);
-    if (rc || n == 0) return rc;
-    lio::DbscanCounts dc;
-    rc = lio::dbscan(f->dn, f->cl, f->d_in, n, stride, eps, min_samples, cap_clusters, &dc, f->st);
-    if (rc) return status(rc, "lio_dbscan");
-    return cluster_download(f, n, {dc.finite, dc.core, dc.clusters, dc.clustered_points}, labels_out, core_opt, n_clusters,
-                            cap_clusters, offsets_opt, indices_opt, aabb6_opt, stats4_opt);
-}
-
-// ---- GPS-to-SLAM trajectory alignment and map georeferencing (lio_gpsalign.hip) ----
-static_assert(lio::kGaLen == LIO_GPSALIGN_LEN && lio::kGaIters == LIO_GPSALIGN_ITERATIONS &&
-                  lio::kGaConverged == LIO_GPSALIGN_CONVERGED && lio::kGaMeanError == LIO_GPSALIGN_MEAN_ERROR &&
-                  lio::kGaS0 == LIO_GPSALIGN_S0 && lio::kGaCA == LIO_GPSALIGN_CA && lio::kGaCB == LIO_GPSALIGN_CB &&
-                  lio::kGaSc == LIO_GPSALIGN_SC && lio::kGaC == LIO_GPSALIGN_C && lio::kGaS == LIO_GPSALIGN_S &&
-                  lio::kGaT == LIO_GPSALIGN_T && lio::kGaCD == LIO_GPSALIGN_CD && lio::kGaRefScale == LIO_GPSALIGN_REF_SCALE &&
-                  lio::kGaRefC == LIO_GPSALIGN_REF_C && lio::kGaRefS == LIO_GPSALIGN_REF_S &&
-                  lio::kGaRefT == LIO_GPSALIGN_REF_T && lio::kGaTotScale == LIO_GPSALIGN_TOTAL_SCALE &&
-                  lio::kGaTotC == LIO_GPSALIGN_TOTAL_C && lio::kGaTotS == LIO_GPSALIGN_TOTAL_S &&
-                  lio::kGaTotT == LIO_GPSALIGN_TOTAL_T && lio::kSimLen == LIO_SIM2D_LEN && lio::kSimScale == LIO_SIM2D_SCALE &&
-                  lio::kSimC == LIO_SIM2D_C && lio::kSimS == LIO_SIM2D_S && lio::kSimT == LIO_SIM2D_T &&
-                  lio::kGaState == LIO_ERR_STATE,
-              "the result offsets of lio_gpsalign.hpp are the public ones");
-
-static bool all_finite(const double* v, int64_t count) {
-    for (int64_t i = 0; i < count; ++i)
-        if (!std::isfinite(v[i])) return false;
-    return true;
-}
-
-// the status of the two fits: kGaState carries its own text
-static int fit_status(int rc, const char* what, const char* arg_what) {
-    if (rc == lio::kGaState) return fail(LIO_ERR_STATE, std::string(what) + ": " + lio::last_error());
-    return status(rc, what, arg_what);
-}
-
-int lio_gps_align(lio_filter* f, const double* gps_xy, int64_t m, const double* slam_xy, int64_t n, int max_iterations,
-                  double tolerance, double* aligned_xy_out, int32_t* nn_out_opt, double* out) {
-    const int rc = denoise_handle(f, "lio_gps_align");
-    if (rc) return rc;
-    if (!gps_xy || !slam_xy || !aligned_xy_out || !out || n < 1 || m < 1 || n >= (int64_t)1 << 31 ||
-        m >= (int64_t)1 << 31 || max_iterations < 1)
-        return fail(LIO_ERR_ARG, "lio_gps_align: bad arguments");
-    if (!all_finite(gps_xy, 2 * m) || !all_finite(slam_xy, 2 * n))
-        return fail(LIO_ERR_ARG, "lio_gps_align: a coordinate is not finite");
-    HIP_TRY(hipSetDevice(f->dev));
-    return fit_status(lio::gps_align(f->ga, gps_xy, m, slam_xy, n, max_iterations, tolerance, aligned_xy_out, nn_out_opt,
-                                     out, f->st),
-                      "lio_gps_align", "a point set has zero variance");
-}
-
-int lio_similarity2d_fit(lio_filter* f, const double* src_xy, const double* dst_xy, int64_t n, double* out) {
-    const int rc = denoise_handle(f, "lio_similarity2d_fit");
-    if (rc) return rc;
-    if (!src_xy || !dst_xy || !out || n < 1 || n >= (int64_t)1 << 31)
-        return fail(LIO_ERR_ARG, "lio_similarity2d_fit: bad arguments");
-    if (!all_finite(src_xy, 2 * n) || !all_finite(dst_xy, 2 * n))
-        return fail(LIO_ERR_ARG, "lio_similarity2d_fit: a coordinate is not finite");
-    HIP_TRY(hipSetDevice(f->dev));
-    return fit_status(lio::similarity2d_fit(f->ga, src_xy, dst_xy, n, out, f->st), "lio_similarity2d_fit", "bad arguments");
-}
-
-int lio_georeference_xy(lio_filter* f, const float* pts, int64_t n, int stride, double scale, const double* R4,
-                        const double* t2, const double* origin2_opt, float* out, double* xy_out_opt) {
-    int rc = denoise_handle(f, "lio_georeference_xy");
-    if (rc) return rc;
-    if (!R4 || !t2 || n < 0 || n >= (int64_t)1 << 31 || (n > 0 && (!pts || !out)) || stride < 3 || stride > lio::kMaxFields)
-        return fail(LIO_ERR_ARG, "lio_georeference_xy: bad arguments");
-    if (n == 0) return LIO_OK;
-    HIP_TRY(hipSetDevice(f->dev));
-    if ((rc = upload_in(f, pts, n * stride))) return rc;
-    if ((rc = grow(&f->d_out, f->out_cap, n * stride))) return rc;
-    if (xy_out_opt && (rc = grow(&f->ga.geo_xy, f->ga.geo_cap, n, 2))) return rc;
-    const double p[9] = {R4[0], R4[1], R4[2], R4[3], scale, t2[0], t2[1], origin2_opt ? origin2_opt[0] : 0.0,
-                         origin2_opt ? origin2_opt[1] : 0.0};
-    rc = lio::georeference_xy(f->d_in, n, stride, p, f->d_out, xy_out_opt ? f->ga.geo_xy : nullptr, f->st);
-    if (rc) return status(rc, "lio_georeference_xy");
-    HIP_TRY(hipMemcpyAsync(out, f->d_out, (size_t)n * stride * sizeof(float), hipMemcpyDeviceToHost, f->st));
-    if (xy_out_opt)
-        HIP_TRY(hipMemcpyAsync(xy_out_opt, f->ga.geo_xy, (size_t)n * 2 * sizeof(double), hipMemcpyDeviceToHost, f->st));
-    HIP_TRY(hipStreamSynchronize(f->st));
-    return LIO_OK;
-}
-
-// ---- camera projection and point cloud colorization (lio_colorize.hip) ----
-// The camera and pose checks shared by lio_project_points and lio_colorizer_add_frame: every failure names its bound.
-static int camera_arg(const std::string& what, const lio_camera* cam, const double* Rt, lio::CamArg* a) {
-    if (!cam) return fail(LIO_ERR_ARG, what + ": cam is NULL");
-    if (!Rt) return fail(LIO_ERR_ARG, what + ": Rt is NULL");
-    if (cam->width < 1 || cam->height < 1) return fail(LIO_ERR_ARG, what + ": width and height must be at least 1");
-    if ((int64_t)cam->width * (int64_t)cam->height >= (int64_t)1 << 31)
-        return fail(LIO_ERR_ARG, what + ": width x height must be below 2^31");
-    const double k[4] = {cam->fx, cam->fy, cam->cx, cam->cy};
-    if (!all_finite(k, 4)) return fail(LIO_ERR_ARG, what + ": an intrinsic (fx, fy, cx, cy) is not finite");
-    if (!all_finite(cam->dist, 8)) return fail(LIO_ERR_ARG, what + ": a distortion coefficient is not finite");
-    if (!all_finite(Rt, 12)) return fail(LIO_ERR_ARG, what + ": a pose entry of Rt is not finite");
-    if (!(cam->r2_max >= 0.0)) return fail(LIO_ERR_ARG, what + ": r2_max must be >= 0 (+inf: no limit) and not NaN");
-    a->fx = cam->fx, a->fy = cam->fy, a->cx = cam->cx, a->cy = cam->cy;
-    a->k1 = cam->dist[0], a->k2 = cam->dist[1], a->p1 = cam->dist[2], a->p2 = cam->dist[3];
-    a->k3 = cam->dist[4], a->k4 = cam->dist[5], a->k5 = cam->dist[6], a->k6 = cam->dist[7];
-    a->r2_max = cam->r2_max;
-    for (int i = 0; i < 9; ++i) a->R[i] = Rt[i];
-    for (int i = 0; i < 3; ++i) a->t[i] = Rt[9 + i];
-    a->width = cam->width, a->height = cam->height;
-    return LIO_OK;
-}
-
-static int cloud_arg(const std::string& what, const float* pts, int64_t n, int stride) {
-    if (n < 0 || n >= (int64_t)1 << 31) return fail(LIO_ERR_ARG, what + ": n must be in 0 .. 2^31 - 1");
-    if (stride < 3 || stride > lio::kMaxFields) return fail(LIO_ERR_ARG, what + ": stride must be in 3..8");
-    if (!pts && n > 0) return fail(LIO_ERR_ARG, what + ": pts is NULL");
-    return LIO_OK;
-}
-
-int lio_project_points(lio_filter* f, const float* pts, int64_t n, int stride, const lio_camera* cam, const double* Rt,
-                       double* uv_opt, double* zc_opt, int32_t* pix_opt, uint8_t* valid) {
-    const char* what = "lio_project_points";
-    int rc = denoise_handle(f, what);
-    if (rc) return rc;
-    if ((rc = cloud_arg(what, pts, n, stride))) return rc;
-    lio::CamArg a{};
-    if ((rc = camera_arg(what, cam, Rt, &a))) return rc;
-    if (!valid) return fail(LIO_ERR_ARG, std::string(what) + ": valid is NULL");
-    if (n == 0) return LIO_OK;
-    HIP_TRY(hipSetDevice(f->dev));
-    if ((rc = upload_in(f, pts, n * stride))) return rc;
-    return status(lio::project_points(f->pj, f->d_in, n, stride, a, uv_opt, zc_opt, pix_opt, valid, f->st), what);
-}
-
-static const lio_colorize_params kColorizeDefaults = {0, 0, 0.f, 0.f, 1};
-
-static int colorize_params_arg(const char* what, const lio_colorize_params* p) {
-    if (p->splat_radius < 0 || p->splat_radius > lio::kCzMaxSplat)
-        return fail(LIO_ERR_ARG, std::string(what) + ": splat_radius must be in 0..8");
-    if (!(p->depth_rel >= 0.f) || !std::isfinite(p->depth_rel) || !(p->depth_abs >= 0.f) || !std::isfinite(p->depth_abs))
-        return fail(LIO_ERR_ARG, std::string(what) + ": depth_rel and depth_abs must be finite and >= 0");
-    return LIO_OK;
-}
-
-struct lio_colorizer {
-    int dev = 0;
-    hipStream_t st = nullptr;
-    lio_colorize_params p = kColorizeDefaults;
-    lio::ColorizeBuf c;
-};
-
-int lio_colorizer_create(int device, const lio_colorize_params* params, lio_colorizer** out) {
-    if (!out) return fail(LIO_ERR_ARG, "lio_colorizer_create: out is NULL");
-    *out = nullptr;
-    int rc = check_device(device);
-    if (rc) return rc;
-    if (params && (rc = colorize_params_arg("lio_colorizer_create", params))) return rc;
-    HIP_TRY(hipSetDevice(device));
-    auto* h = new lio_colorizer();
-    h->dev = device;
-    if (params) h->p = *params;
-    if (hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking) != hipSuccess) {
-        delete h;
-        return fail(LIO_ERR_HIP, "hipStreamCreate failed");
-    }
-    if ((rc = lio::colorizer_init(h->c))) {
-        lio::colorizer_free(h->c);
-        (void)hipStreamDestroy(h->st);
-        delete h;
-        return status(rc, "lio_colorizer_create");
-    }
-    *out = h;
-    return LIO_OK;
-}
-
-int lio_colorizer_destroy(lio_colorizer* h) {
-    if (!h) return LIO_OK;
-    (void)hipSetDevice(h->dev);
-    (void)hipStreamSynchronize(h->st);
-    lio::colorizer_free(h->c);
-    (void)hipStreamDestroy(h->st);
-    delete h;
-    return LIO_OK;
-}
-
-// a NULL handle without a device is the missing device (lio_colorizer_create cannot have succeeded)
-static int colorizer_handle(lio_colorizer* h, const char* what) {
-    if (h) return LIO_OK;
-    const int rc = check_device(0);
-    if (rc) return rc;
-    return fail(LIO_ERR_ARG, std::string(what) + ": handle is NULL");
-}
-
-int lio_colorizer_set_params(lio_colorizer* h, const lio_colorize_params* params) {
-    int rc = colorizer_handle(h, "lio_colorizer_set_params");
-    if (rc) return rc;
-    if (!params) return fail(LIO_ERR_ARG, "lio_colorizer_set_params: params is NULL");
-    if ((rc = colorize_params_arg("lio_colorizer_set_params", params))) return rc;
-    h->p = *params;
-    return LIO_OK;
-}
-
-int lio_colorizer_set_cloud(lio_colorizer* h, const float* pts, int64_t n, int stride) {
-    const char* what = "lio_colorizer_set_cloud";
-    int rc = colorizer_handle(h, what);
-    if (rc) return rc;
-    if ((rc = cloud_arg(what, pts, n, stride))) return rc;
-    HIP_TRY(hipSetDevice(h->dev));
-    return status(lio::colorizer_set_cloud(h->c, pts, n, stride, h->st), what);
-}
-
-int lio_colorizer_add_frame(lio_colorizer* h, const lio_camera* cam, const double* Rt, const uint8_t* image, int64_t pitch,
-                            int64_t* n_updated) {
-    const std::string what = "lio_colorizer_add_frame";
-    int rc = colorizer_handle(h, what.c_str());
-    if (rc) return rc;
-    lio::CamArg a{};
-    if ((rc = camera_arg(what, cam, Rt, &a))) return rc;
-    if (!image) return fail(LIO_ERR_ARG, what + ": image is NULL");
-    if (!n_updated) return fail(LIO_ERR_ARG, what + ": n_updated is NULL");
-    if (pitch < 3 * (int64_t)cam->width) return fail(LIO_ERR_ARG, what + ": pitch must be at least 3 x width bytes");
-    if (!h->c.have_cloud) return fail(LIO_ERR_STATE, what + ": no cloud (call lio_colorizer_set_cloud first)");
-    *n_updated = 0;
-    HIP_TRY(hipSetDevice(h->dev));
-    return status(lio::colorizer_add_frame(h->c, a, image, pitch, h->p.bgr != 0, h->p.occlusion != 0, h->p.splat_radius,
-                                           h->p.depth_rel, h->p.depth_abs, n_updated, h->st),
-                  what.c_str());
-}
-
-int lio_colorizer_get(lio_colorizer* h, uint8_t* rgb, int32_t* frame_opt, double* depth_opt) {
-    int rc = colorizer_handle(h, "lio_colorizer_get");
-    if (rc) return rc;
-    if (!rgb) return fail(LIO_ERR_ARG, "lio_colorizer_get: rgb is NULL");
-    if (!h->c.have_cloud) return fail(LIO_ERR_STATE, "lio_colorizer_get: no cloud (call lio_colorizer_set_cloud first)");
-    HIP_TRY(hipSetDevice(h->dev));
-    return status(lio::colorizer_get(h->c, rgb, frame_opt, depth_opt, h->st), "lio_colorizer_get");
-}
-
-int lio_colorizer_reset(lio_colorizer* h) {
-    int rc = colorizer_handle(h, "lio_colorizer_reset");
-    if (rc) return rc;
-    HIP_TRY(hipSetDevice(h->dev));
-    return status(lio::colorizer_reset(h->c, h->st), "lio_colorizer_reset");
-}
-
-int lio_colorizer_get_timing(lio_colorizer* h, double* ms4) {
-    int rc = colorizer_handle(h, "lio_colorizer_get_timing");
-    if (rc) return rc;
-    if (!ms4) return fail(LIO_ERR_ARG, "lio_colorizer_get_timing: ms4 is NULL");
-    for (int k = 0; k < lio::kCzStages; ++k) ms4[k] = h->c.ms[k];
-    return LIO_OK;
-}
-
-// ---- image undistortion (lio_undistort.hip) ----
-// The camera checks shared by lio_undistort_map and lio_undistorter_set_camera; they need no device and come before
-// the handle is looked at.  dst_opt NULL: src's intrinsics and size.
-static int undistort_cams_arg(const std::string& what, const lio_camera* src, const lio_camera* dst_opt, lio::CamArg* a,
-                              lio::UdDst* d) {
-    if (!src) return fail(LIO_ERR_ARG, what + ": src is NULL");
-    const lio_camera* dst = dst_opt ? dst_opt : src;
-    for (const lio_camera* c : {src, dst})
-        if (c->width < 1 || c->width > lio::kUdMaxSize || c->height < 1 || c->height > lio::kUdMaxSize)
-            return fail(LIO_ERR_ARG, what + ": width and height must be in 1..32767");
-    const double k[8] = {src->fx, src->fy, src->cx, src->cy, dst->fx, dst->fy, dst->cx, dst->cy};
-    if (!all_finite(k, 8)) return fail(LIO_ERR_ARG, what + ": an intrinsic (fx, fy, cx, cy) is not finite");
-    if (!all_finite(src->dist, 8)) return fail(LIO_ERR_ARG, what + ": a distortion coefficient is not finite");
-    if (dst->fx == 0.0 || dst->fy == 0.0) return fail(LIO_ERR_ARG, what + ": dst fx and fy must not be 0");
-    if (dst_opt)
-        for (double v : dst_opt->dist)
-            if (!(v == 0.0)) return fail(LIO_ERR_ARG, what + ": dst dist must be all zero (the rectified image is a pinhole)");
-    *a = lio::CamArg{};
-    a->fx = src->fx, a->fy = src->fy, a->cx = src->cx, a->cy = src->cy;
-    a->k1 = src->dist[0], a->k2 = src->dist[1], a->p1 = src->dist[2], a->p2 = src->dist[3];
-    a->k3 = src->dist[4], a->k4 = src->dist[5], a->k5 = src->dist[6], a->k6 = src->dist[7];
-    a->r2_max = std::numeric_limits<double>::infinity();
-    a->width = src->width, a->height = src->height;
-    *d = lio::UdDst{dst->fx, dst->fy, dst->cx, dst->cy, dst->width, dst->height};
-    return LIO_OK;
-}
-
-int lio_undistort_map(lio_filter* f, const lio_camera* src, const lio_camera* dst_opt, double* uv_opt, int32_t* sxy_opt,
-                      uint8_t* axy_opt) {
-    const char* what = "lio_undistort_map";
-    lio::CamArg a{};
-    lio::UdDst d{};
-    int rc = undistort_cams_arg(what, src, dst_opt, &a, &d);
-    if (rc) return rc;
-    if ((rc = denoise_handle(f, what))) return rc;
-    HIP_TRY(hipSetDevice(f->dev));
-    return status(lio::undistort_map(f->pj, a, d, uv_opt, sxy_opt, axy_opt, f->st), what);
-}
-
-struct lio_undistorter {
-    int dev = 0;
-    hipStream_t st = nullptr;
-    lio::UndistortBuf u;
-};
-
-int lio_undistorter_create(int device, lio_undistorter** out) {
-    if (!out) return fail(LIO_ERR_ARG, "lio_undistorter_create: out is NULL");
-    *out = nullptr;
-    int rc = check_device(device);
-    if (rc) return rc;
-    HIP_TRY(hipSetDevice(device));
-    auto* h = new lio_undistorter();
-    h->dev = device;
-    if (hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking) != hipSuccess) {
-        delete h;
-        return fail(LIO_ERR_HIP, "hipStreamCreate failed");
-    }
-    if ((rc = lio::undistorter_init(h->u))) {
-        lio::undistorter_free(h->u);
-        (void)hipStreamDestroy(h->st);
-        delete h;
-        return status(rc, "lio_undistorter_create");
-    }
-    *out = h;
-    return LIO_OK;
-}
-
-int lio_undistorter_destroy(lio_undistorter* h) {
-    if (!h) return LIO_OK;
-    (void)hipSetDevice(h->dev);
-    (void)hipStreamSynchronize(h->st);
-    lio::undistorter_free(h->u);
-    (void)hipStreamDestroy(h->st);
-    delete h;
-    return LIO_OK;
-}
-
-// a NULL handle without a device is the missing device (lio_undistorter_create cannot have succeeded)
-static int undistorter_handle(lio_undistorter* h, const char* what) {
-    if (h) return LIO_OK;
-    const int rc = check_device(0);
-    if (rc) return rc;
-    return fail(LIO_ERR_ARG, std::string(what) + ": handle is NULL");
-}
-
-int lio_undistorter_set_camera(lio_undistorter* h, const lio_camera* src, const lio_camera* dst_opt, int channels,
-                               const uint8_t* border_opt) {
-    const char* what = "lio_undistorter_set_camera";
-    lio::CamArg a{};
-    lio::UdDst d{};
-    int rc = undistort_cams_arg(what, src, dst_opt, &a, &d);
-    if (rc) return rc;
-    if (channels != 1 && channels != 3) return fail(LIO_ERR_ARG, std::string(what) + ": channels must be 1 or 3");
-    if ((rc = undistorter_handle(h, what))) return rc;
-    const uint8_t black[3] = {0, 0, 0};
-    HIP_TRY(hipSetDevice(h->dev));
-    return status(lio::undistorter_set_camera(h->u, a, d, channels, border_opt ? border_opt : black, h->st), what);
-}
-
-int lio_undistorter_run(lio_undistorter* h, const uint8_t* image, int64_t pitch, uint8_t* out, int64_t out_pitch) {
-    const std::string what = "lio_undistorter_run";
-    if (!image) return fail(LIO_ERR_ARG, what + ": image is NULL");
-    if (!out) return fail(LIO_ERR_ARG, what + ": out is NULL");
-    const int rc = undistorter_handle(h, what.c_str());
-    if (rc) return rc;
-    if (!h->u.have_camera) return fail(LIO_ERR_STATE, what + ": no camera (call lio_undistorter_set_camera first)");
-    if (pitch < (int64_t)h->u.channels * h->u.sw)
-        return fail(LIO_ERR_ARG, what + ": pitch must be at least channels x width bytes of the raw image");
-    if (out_pitch < (int64_t)h->u.channels * h->u.dw)
-        return fail(LIO_ERR_ARG, what + ": out_pitch must be at least channels x width bytes of the rectified image");
-    HIP_TRY(hipSetDevice(h->dev));
-    return status(lio::undistorter_run(h->u, image, pitch, out, out_pitch, h->st), what.c_str());
-}
-
-int lio_undistorter_get_timing(lio_undistorter* h, double* ms3) {
-    const int rc = undistorter_handle(h, "lio_undistorter_get_timing");
-    if (rc) return rc;
-    if (!ms3) return fail(LIO_ERR_ARG, "lio_undistorter_get_timing: ms3 is NULL");
-    for (int k = 0; k < lio::kUdStages; ++k) ms3[k] = h->u.ms[k];
-    return LIO_OK;
-}
-
-// ---- RANSAC plane segmentation (lio_plane.hip) ----
-int lio_plane_sample_triples(uint64_t seed, int64_t n, int64_t num_iterations, int32_t* out) {
-    if (n < 0 || n >= (int64_t)1 << 31 || num_iterations < 0 || num_iterations > (int64_t)1 << 20 ||
-        (n >= 3 && num_iterations > 0 && !out))
-        return fail(LIO_ERR_ARG, "lio_plane_sample_triples: bad arguments");
-    if (n >= 3) lio::plane_sample_triples(seed, n, num_iterations, out);
-    return LIO_OK;
-}
-
-int lio_segment_plane(lio_filter* f, const float* pts, int64_t n, int stride, float distance_threshold, int ransac_n,
-                      int64_t num_iterations, uint64_t seed, const int32_t* triples_opt, float* plane4_out,
-                      int64_t* best_iteration, int32_t* inliers_out, int64_t* n_inliers, uint8_t* mask_opt,
-                      int64_t* counts_opt, uint64_t* sq_opt, uint8_t* degenerate_opt, double* refit4_opt) {
-    int rc = denoise_handle(f, "lio_segment_plane");
-    if (rc) return rc;
-    const int64_t K = num_iterations;
-    const float thr2 = distance_threshold * distance_threshold;
-    if (!plane4_out || !best_iteration || !n_inliers || n < 0 || n >= (int64_t)1 << 31 || (n > 0 && (!pts || !inliers_out)) ||
-        stride < 3 || stride > lio::kMaxFields || !(distance_threshold > 0.f) || !std::isfinite(distance_threshold) ||
-        !std::isfinite(thr2) || ransac_n != 3 || K < 1 || K > (int64_t)1 << 20)
-        return fail(LIO_ERR_ARG, "lio_segment_plane: bad arguments");
-    if (triples_opt && !lio::plane_triples_valid(triples_opt, K, n))
-        return fail(LIO_ERR_ARG, "lio_segment_plane: a triple holds an index outside [0, n) or a repeated index");
-    for (int k = 0; k < 4; ++k) plane4_out[k] = 0.f;
-    *best_iteration = -1;
-    *n_inliers = 0;
-    if (refit4_opt)
-        for (int k = 0; k < 4; ++k) refit4_opt[k] = 0.0;
-    if (n < 3) {  // no hypothesis at all: every entry counts as skipped
-        if (mask_opt && n) std::memset(mask_opt, 0, (size_t)n);
-        if (counts_opt) std::memset(counts_opt, 0, (size_t)K * sizeof(int64_t));
-        if (sq_opt) std::memset(sq_opt, 0, (size_t)K * sizeof(uint64_t));
-        if (degenerate_opt) std::memset(degenerate_opt, 1, (size_t)K);
-        return LIO_OK;
-    }
-    lio::PlaneBuf& pb = f->pl;
-    if ((int64_t)pb.h_planes.size() < 4 * K) pb.h_planes.resize((size_t)(4 * K));
-    if ((int64_t)pb.h_deg.size() < K) pb.h_deg.resize((size_t)K);
-    const int32_t* tri = triples_opt;
-    if (!tri) {
-        if ((int64_t)pb.h_tri.size() < 3 * K) pb.h_tri.resize((size_t)(3 * K));
-        lio::plane_sample_triples(seed, n, K, pb.h_tri.data());
-        tri = pb.h_tri.data();
-    }
-    lio::plane_hypotheses(pts, stride, tri, K, pb.h_planes.data(), pb.h_deg.data());
-    HIP_TRY(hipSetDevice(f->dev));
-    if ((rc = upload_in(f, pts, n * stride))) return rc;
-    lio::PlaneResult pr;
-    rc = lio::segment_plane(f->dn, pb, f->d_in, pts, n, stride, distance_threshold, K, refit4_opt != nullptr, &pr, f->st);
-    if (rc) return status(rc, "lio_segment_plane");
-    if (pr.n_inliers)
-        HIP_TRY(hipMemcpyAsync(inliers_out, pb.inliers, (size_t)pr.n_inliers * sizeof(int32_t), hipMemcpyDeviceToHost, f->st));
-    if (mask_opt) HIP_TRY(hipMemcpyAsync(mask_opt, pb.mask, (size_t)n, hipMemcpyDeviceToHost, f->st));
-    if (counts_opt) HIP_TRY(hipMemcpyAsync(counts_opt, pb.cnt, (size_t)K * sizeof(int64_t), hipMemcpyDeviceToHost, f->st));
-    if (sq_opt) HIP_TRY(hipMemcpyAsync(sq_opt, pb.sq, (size_t)K * sizeof(uint64_t), hipMemcpyDeviceToHost, f->st));
-    HIP_TRY(hipStreamSynchronize(f->st));
-    if (degenerate_opt) std::memcpy(degenerate_opt, pb.h_deg.data(), (size_t)K);
-    std::memcpy(plane4_out, pr.plane, sizeof(pr.plane));
-    *best_iteration = pr.best;
-    *n_inliers = pr.n_inliers;
-    if (refit4_opt) std::memcpy(refit4_opt, pr.refit, sizeof(pr.refit));
-    return LIO_OK;
+    return download_out(f, m, stride, out, n_out);
 }
 
 int lio_submap_voxelize(lio_filter* f, const float* pts, const int64_t* seg_off, int nk, int stride,
@@ -1939,10 +1248,7 @@ int lio_submap_voxelize(lio_filter* f, const float* pts, const int64_t* seg_off,
     int64_t m = 0;
     rc = lio::voxel_grid(f->b, d_tf, n, stride, leaf, f->d_out, &m, f->st);
     if (rc) return status(rc, "lio_submap_voxelize");
-    if (m) HIP_TRY(hipMemcpyAsync(out, f->d_out, (size_t)m * stride * sizeof(float), hipMemcpyDeviceToHost, f->st));
-    HIP_TRY(hipStreamSynchronize(f->st));
-    *n_out = m;
-    return LIO_OK;
+    return download_out(f, m, stride, out, n_out);
 }
 
 static int prep_args_ok(const float* raw, int64_t n, int stride, const lio_scan_prep_params* p,

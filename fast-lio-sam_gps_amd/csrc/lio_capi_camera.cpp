@@ -1,0 +1,254 @@
+// lio_capi_camera.cpp — the C-ABI (include/lio_gpu.h) of the camera leg: lio_project_points and
+// lio_undistort_map on a lio_filter, the lio_colorizer and the lio_undistorter.
+#include <limits>
+
+#include "lio_capi_util.hpp"
+#include "lio_colorize.hpp"
+#include "lio_undistort.hpp"
+
+using namespace lio::capi;
+
+extern "C" {
+
+// ---- the camera of both halves ----
+// the finite checks: the intrinsics of cam and of the second camera (cam again where there is one), then cam's
+// coefficients
+static int camera_finite(const std::string& what, const lio_camera* cam, const lio_camera* second) {
+    const double k[8] = {cam->fx, cam->fy, cam->cx, cam->cy, second->fx, second->fy, second->cx, second->cy};
+    if (!all_finite(k, 8)) return fail(LIO_ERR_ARG, what + ": an intrinsic (fx, fy, cx, cy) is not finite");
+    if (!all_finite(cam->dist, 8)) return fail(LIO_ERR_ARG, what + ": a distortion coefficient is not finite");
+    return LIO_OK;
+}
+
+// cam's intrinsics, coefficients and size; R and t stay zero and r2_max has no limit
+static lio::CamArg cam_arg(const lio_camera* cam) {
+    lio::CamArg a{};
+    a.fx = cam->fx, a.fy = cam->fy, a.cx = cam->cx, a.cy = cam->cy;
+    a.k1 = cam->dist[0], a.k2 = cam->dist[1], a.p1 = cam->dist[2], a.p2 = cam->dist[3];
+    a.k3 = cam->dist[4], a.k4 = cam->dist[5], a.k5 = cam->dist[6], a.k6 = cam->dist[7];
+    a.r2_max = std::numeric_limits<double>::infinity();
+    a.width = cam->width, a.height = cam->height;
+    return a;
+}
+
+// ---- camera projection and point cloud colorization (lio_colorize.hip) ----
+// The camera and pose checks shared by lio_project_points and lio_colorizer_add_frame: every failure names its bound.
+static int camera_arg(const std::string& what, const lio_camera* cam, const double* Rt, lio::CamArg* a) {
+    if (!cam) return fail(LIO_ERR_ARG, what + ": cam is NULL");
+    if (!Rt) return fail(LIO_ERR_ARG, what + ": Rt is NULL");
+    if (cam->width < 1 || cam->height < 1) return fail(LIO_ERR_ARG, what + ": width and height must be at least 1");
+    if ((int64_t)cam->width * (int64_t)cam->height >= (int64_t)1 << 31)
+        return fail(LIO_ERR_ARG, what + ": width x height must be below 2^31");
+    if (const int rc = camera_finite(what, cam, cam)) return rc;
+    if (!all_finite(Rt, 12)) return fail(LIO_ERR_ARG, what + ": a pose entry of Rt is not finite");
+    if (!(cam->r2_max >= 0.0)) return fail(LIO_ERR_ARG, what + ": r2_max must be >= 0 (+inf: no limit) and not NaN");
+    *a = cam_arg(cam);
+    a->r2_max = cam->r2_max;
+    for (int i = 0; i < 9; ++i) a->R[i] = Rt[i];
+    for (int i = 0; i < 3; ++i) a->t[i] = Rt[9 + i];
+    return LIO_OK;
+}
+
+static int cloud_arg(const std::string& what, const float* pts, int64_t n, int stride) {
+    if (n < 0 || n >= (int64_t)1 << 31) return fail(LIO_ERR_ARG, what + ": n must be in 0 .. 2^31 - 1");
+    if (stride < 3 || stride > lio::kMaxFields) return fail(LIO_ERR_ARG, what + ": stride must be in 3..8");
+    if (!pts && n > 0) return fail(LIO_ERR_ARG, what + ": pts is NULL");
+    return LIO_OK;
+}
+
+int lio_project_points(lio_filter* f, const float* pts, int64_t n, int stride, const lio_camera* cam, const double* Rt,
+                       double* uv_opt, double* zc_opt, int32_t* pix_opt, uint8_t* valid) {
+    const char* what = "lio_project_points";
+    int rc = null_handle(f, what);
+    if (rc) return rc;
+    if ((rc = cloud_arg(what, pts, n, stride))) return rc;
+    lio::CamArg a{};
+    if ((rc = camera_arg(what, cam, Rt, &a))) return rc;
+    if (!valid) return fail(LIO_ERR_ARG, std::string(what) + ": valid is NULL");
+    if (n == 0) return LIO_OK;
+    HIP_TRY(hipSetDevice(f->dev));
+    if ((rc = upload_in(f, pts, n * stride))) return rc;
+    return status(lio::project_points(f->pj, f->d_in, n, stride, a, uv_opt, zc_opt, pix_opt, valid, f->st), what);
+}
+
+static const lio_colorize_params kColorizeDefaults = {0, 0, 0.f, 0.f, 1};
+
+static int colorize_params_arg(const char* what, const lio_colorize_params* p) {
+    if (p->splat_radius < 0 || p->splat_radius > lio::kCzMaxSplat)
+        return fail(LIO_ERR_ARG, std::string(what) + ": splat_radius must be in 0..8");
+    if (!(p->depth_rel >= 0.f) || !std::isfinite(p->depth_rel) || !(p->depth_abs >= 0.f) || !std::isfinite(p->depth_abs))
+        return fail(LIO_ERR_ARG, std::string(what) + ": depth_rel and depth_abs must be finite and >= 0");
+    return LIO_OK;
+}
+
+struct lio_colorizer : Handle {
+    lio_colorize_params p = kColorizeDefaults;
+    lio::ColorizeBuf c;
+};
+
+int lio_colorizer_destroy(lio_colorizer* h) {
+    return close_handle(h, [](lio_colorizer& z) { lio::colorizer_free(z.c); });
+}
+
+// a handle whose params or init fail is closed again: *out stays NULL
+int lio_colorizer_create(int device, const lio_colorize_params* params, lio_colorizer** out) {
+    int rc = open_handle(device, out, "lio_colorizer_create: out is NULL");
+    if (rc) return rc;
+    lio_colorizer* h = *out;
+    if (params && !(rc = colorize_params_arg("lio_colorizer_create", params))) h->p = *params;
+    if (!rc) rc = status(lio::colorizer_init(h->c), "lio_colorizer_create");
+    if (rc) {
+        *out = nullptr;
+        lio_colorizer_destroy(h);
+    }
+    return rc;
+}
+
+int lio_colorizer_set_params(lio_colorizer* h, const lio_colorize_params* params) {
+    int rc = null_handle(h, "lio_colorizer_set_params");
+    if (rc) return rc;
+    if (!params) return fail(LIO_ERR_ARG, "lio_colorizer_set_params: params is NULL");
+    if ((rc = colorize_params_arg("lio_colorizer_set_params", params))) return rc;
+    h->p = *params;
+    return LIO_OK;
+}
+
+int lio_colorizer_set_cloud(lio_colorizer* h, const float* pts, int64_t n, int stride) {
+    const char* what = "lio_colorizer_set_cloud";
+    int rc = null_handle(h, what);
+    if (rc) return rc;
+    if ((rc = cloud_arg(what, pts, n, stride))) return rc;
+    HIP_TRY(hipSetDevice(h->dev));
+    return status(lio::colorizer_set_cloud(h->c, pts, n, stride, h->st), what);
+}
+
+int lio_colorizer_add_frame(lio_colorizer* h, const lio_camera* cam, const double* Rt, const uint8_t* image, int64_t pitch,
+                            int64_t* n_updated) {
+    const std::string what = "lio_colorizer_add_frame";
+    int rc = null_handle(h, what.c_str());
+    if (rc) return rc;
+    lio::CamArg a{};
+    if ((rc = camera_arg(what, cam, Rt, &a))) return rc;
+    if (!image) return fail(LIO_ERR_ARG, what + ": image is NULL");
+    if (!n_updated) return fail(LIO_ERR_ARG, what + ": n_updated is NULL");
+    if (pitch < 3 * (int64_t)cam->width) return fail(LIO_ERR_ARG, what + ": pitch must be at least 3 x width bytes");
+    if (!h->c.have_cloud) return fail(LIO_ERR_STATE, what + ": no cloud (call lio_colorizer_set_cloud first)");
+    *n_updated = 0;
+    HIP_TRY(hipSetDevice(h->dev));
+    return status(lio::colorizer_add_frame(h->c, a, image, pitch, h->p.bgr != 0, h->p.occlusion != 0, h->p.splat_radius,
+                                           h->p.depth_rel, h->p.depth_abs, n_updated, h->st),
+                  what.c_str());
+}
+
+int lio_colorizer_get(lio_colorizer* h, uint8_t* rgb, int32_t* frame_opt, double* depth_opt) {
+    int rc = null_handle(h, "lio_colorizer_get");
+    if (rc) return rc;
+    if (!rgb) return fail(LIO_ERR_ARG, "lio_colorizer_get: rgb is NULL");
+    if (!h->c.have_cloud) return fail(LIO_ERR_STATE, "lio_colorizer_get: no cloud (call lio_colorizer_set_cloud first)");
+    HIP_TRY(hipSetDevice(h->dev));
+    return status(lio::colorizer_get(h->c, rgb, frame_opt, depth_opt, h->st), "lio_colorizer_get");
+}
+
+int lio_colorizer_reset(lio_colorizer* h) {
+    int rc = null_handle(h, "lio_colorizer_reset");
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(h->dev));
+    return status(lio::colorizer_reset(h->c, h->st), "lio_colorizer_reset");
+}
+
+int lio_colorizer_get_timing(lio_colorizer* h, double* ms4) {
+    int rc = null_handle(h, "lio_colorizer_get_timing");
+    if (rc) return rc;
+    if (!ms4) return fail(LIO_ERR_ARG, "lio_colorizer_get_timing: ms4 is NULL");
+    for (int k = 0; k < lio::kCzStages; ++k) ms4[k] = h->c.ms[k];
+    return LIO_OK;
+}
+
+// ---- image undistortion (lio_undistort.hip) ----
+// The camera checks shared by lio_undistort_map and lio_undistorter_set_camera; they need no device and come before
+// the handle is looked at.  dst_opt NULL: src's intrinsics and size.
+static int undistort_cams_arg(const std::string& what, const lio_camera* src, const lio_camera* dst_opt, lio::CamArg* a,
+                              lio::UdDst* d) {
+    if (!src) return fail(LIO_ERR_ARG, what + ": src is NULL");
+    const lio_camera* dst = dst_opt ? dst_opt : src;
+    for (const lio_camera* c : {src, dst})
+        if (c->width < 1 || c->width > lio::kUdMaxSize || c->height < 1 || c->height > lio::kUdMaxSize)
+            return fail(LIO_ERR_ARG, what + ": width and height must be in 1..32767");
+    if (const int rc = camera_finite(what, src, dst)) return rc;
+    if (dst->fx == 0.0 || dst->fy == 0.0) return fail(LIO_ERR_ARG, what + ": dst fx and fy must not be 0");
+    if (dst_opt)
+        for (double v : dst_opt->dist)
+            if (!(v == 0.0)) return fail(LIO_ERR_ARG, what + ": dst dist must be all zero (the rectified image is a pinhole)");
+    *a = cam_arg(src);
+    *d = lio::UdDst{dst->fx, dst->fy, dst->cx, dst->cy, dst->width, dst->height};
+    return LIO_OK;
+}
+
+int lio_undistort_map(lio_filter* f, const lio_camera* src, const lio_camera* dst_opt, double* uv_opt, int32_t* sxy_opt,
+                      uint8_t* axy_opt) {
+    const char* what = "lio_undistort_map";
+    lio::CamArg a{};
+    lio::UdDst d{};
+    int rc = undistort_cams_arg(what, src, dst_opt, &a, &d);
+    if (rc) return rc;
+    if ((rc = null_handle(f, what))) return rc;
+    HIP_TRY(hipSetDevice(f->dev));
+    return status(lio::undistort_map(f->pj, a, d, uv_opt, sxy_opt, axy_opt, f->st), what);
+}
+
+struct lio_undistorter : Handle {
+    lio::UndistortBuf u;
+};
+
+int lio_undistorter_destroy(lio_undistorter* h) {
+    return close_handle(h, [](lio_undistorter& z) { lio::undistorter_free(z.u); });
+}
+
+int lio_undistorter_create(int device, lio_undistorter** out) {
+    int rc = open_handle(device, out, "lio_undistorter_create: out is NULL");
+    if (rc) return rc;
+    if ((rc = status(lio::undistorter_init((*out)->u), "lio_undistorter_create"))) {
+        lio_undistorter_destroy(*out);
+        *out = nullptr;
+    }
+    return rc;
+}
+
+int lio_undistorter_set_camera(lio_undistorter* h, const lio_camera* src, const lio_camera* dst_opt, int channels,
+                               const uint8_t* border_opt) {
+    const char* what = "lio_undistorter_set_camera";
+    lio::CamArg a{};
+    lio::UdDst d{};
+    int rc = undistort_cams_arg(what, src, dst_opt, &a, &d);
+    if (rc) return rc;
+    if (channels != 1 && channels != 3) return fail(LIO_ERR_ARG, std::string(what) + ": channels must be 1 or 3");
+    if ((rc = null_handle(h, what))) return rc;
+    const uint8_t black[3] = {0, 0, 0};
+    HIP_TRY(hipSetDevice(h->dev));
+    return status(lio::undistorter_set_camera(h->u, a, d, channels, border_opt ? border_opt : black, h->st), what);
+}
+
+int lio_undistorter_run(lio_undistorter* h, const uint8_t* image, int64_t pitch, uint8_t* out, int64_t out_pitch) {
+    const std::string what = "lio_undistorter_run";
+    if (!image) return fail(LIO_ERR_ARG, what + ": image is NULL");
+    if (!out) return fail(LIO_ERR_ARG, what + ": out is NULL");
+    const int rc = null_handle(h, what.c_str());
+    if (rc) return rc;
+    if (!h->u.have_camera) return fail(LIO_ERR_STATE, what + ": no camera (call lio_undistorter_set_camera first)");
+    if (pitch < (int64_t)h->u.channels * h->u.sw)
+        return fail(LIO_ERR_ARG, what + ": pitch must be at least channels x width bytes of the raw image");
+    if (out_pitch < (int64_t)h->u.channels * h->u.dw)
+        return fail(LIO_ERR_ARG, what + ": out_pitch must be at least channels x width bytes of the rectified image");
+    HIP_TRY(hipSetDevice(h->dev));
+    return status(lio::undistorter_run(h->u, image, pitch, out, out_pitch, h->st), what.c_str());
+}
+
+int lio_undistorter_get_timing(lio_undistorter* h, double* ms3) {
+    const int rc = null_handle(h, "lio_undistorter_get_timing");
+    if (rc) return rc;
+    if (!ms3) return fail(LIO_ERR_ARG, "lio_undistorter_get_timing: ms3 is NULL");
+    for (int k = 0; k < lio::kUdStages; ++k) ms3[k] = h->u.ms[k];
+    return LIO_OK;
+}
+
+}  // extern "C"

@@ -110,20 +110,14 @@ int cluster_reserve(ClusterBuf& c, int64_t n) {
     if (n <= c.cap && c.arena) return kOk;
     const int64_t cap = std::min<int64_t>(grown<int64_t>(n, c.cap, 4096), 0x7fffff00);
     dev_free(&c.arena);
-    c.cap = 0;
+    c.arena_bytes = 0, c.cap = 0;
     const size_t C = (size_t)cap;
-    auto carve = [&](Carver at) {  // the arena's fields, once each, in arena order
+    auto fields = [&](Carver& at) {  // the arena's fields, once each, in arena order
         at(c.parent, C), at(c.run_of, C), at(c.run_start, C + 1), at(c.rank_of, C);
         at(c.labels, C), at(c.indices, C), at(c.offsets, C + 1), at(c.aabb, 6 * C), at(c.cnt, 16);
-        return at.bytes();
     };
-    const size_t total = carve(Carver{});
-    count_alloc();
-    if (hipMalloc(&c.arena, total) != hipSuccess) {
-        c.arena = nullptr;
-        return kNoMem;
-    }
-    carve(Carver{c.arena});
+    const int rc = reserve_arena(&c.arena, c.arena_bytes, fields, 0);
+    if (rc) return rc;
     c.cap = cap;
     return kOk;
 }

@@ -13,6 +13,7 @@ namespace lio {
 // arena sized for `cap` points, grown geometrically (counted: lio_alloc_count).  60 bytes per point.
 struct ClusterBuf {
     void* arena = nullptr;
+    size_t arena_bytes = 0;
     int64_t cap = 0;
     uint32_t* parent = nullptr;     // union-find over input indices
     uint32_t* run_of = nullptr;     // per position of the root-sorted order: its component (run) number

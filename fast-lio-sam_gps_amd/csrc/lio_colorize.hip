@@ -24,22 +24,6 @@
 
 namespace lio {
 
-// pinned host memory of at least `need` bytes, grown geometrically and counted
-int grow_pinned(uint8_t** p, size_t& bytes, size_t need) {
-    if (need <= bytes && *p) return kOk;
-    const size_t c = grown(need, bytes, (size_t)1 << 20);
-    if (*p) (void)hipHostFree(*p);
-    *p = nullptr;
-    bytes = 0;
-    count_alloc();
-    if (hipHostMalloc(reinterpret_cast<void**>(p), c, hipHostMallocDefault) != hipSuccess) {
-        *p = nullptr;
-        return kNoMem;
-    }
-    bytes = c;
-    return kOk;
-}
-
 namespace {
 
 struct Projected {
@@ -179,18 +163,14 @@ int project_points(ProjectBuf& b, const float* d_pts, int64_t n, int stride, con
     double* d_zc = nullptr;
     int2* d_pix = nullptr;
     uint8_t* d_valid = nullptr;
-    auto carve = [&](Carver& c) {
+    auto fields = [&](Carver& c) {
         c(d_uv, uv_opt ? (size_t)n : 0);
         c(d_zc, zc_opt ? (size_t)n : 0);
         c(d_pix, pix_opt ? (size_t)n : 0);
         c(d_valid, (size_t)n);
     };
-    Carver measure;
-    carve(measure);
-    int rc = grow_scratch(&b.arena, b.arena_bytes, measure.bytes());
+    const int rc = reserve_arena(&b.arena, b.arena_bytes, fields);
     if (rc) return rc;
-    Carver assign(b.arena);
-    carve(assign);
     if (!uv_opt) d_uv = nullptr;
     if (!zc_opt) d_zc = nullptr;
     if (!pix_opt) d_pix = nullptr;
@@ -215,8 +195,7 @@ int colorizer_init(ColorizeBuf& c) {
 
 void colorizer_free(ColorizeBuf& c) {
     dev_free(&c.pts, &c.best_z, &c.rgb, &c.frame, &c.img, &c.depth, &c.count);
-    if (c.h_img) (void)hipHostFree(c.h_img);
-    if (c.h_count) (void)hipHostFree(c.h_count);
+    host_free(&c.h_img, &c.h_count);
     for (hipEvent_t e : c.ev)
         if (e) (void)hipEventDestroy(e);
     c = ColorizeBuf{};
@@ -259,7 +238,7 @@ int colorizer_add_frame(ColorizeBuf& c, const CamArg& cam, const uint8_t* image,
     const size_t bytes = (size_t)(cam.height - 1) * (size_t)pitch + (size_t)cam.width * 3;
     const int64_t pixels = (int64_t)cam.width * cam.height;
     const int64_t pixels4 = (pixels + 3) / 4;
-    int rc = grow_pinned(&c.h_img, c.h_img_bytes, bytes);
+    int rc = grow_pinned(&c.h_img, c.h_img_bytes, bytes, kImageStageFloor);
     if (!rc) rc = grow_scratch(reinterpret_cast<void**>(&c.img), c.img_bytes, bytes);
     if (!rc && occlusion) rc = grow_buf(&c.depth, c.depth_cap, pixels4 * 4);
     if (rc) return rc;

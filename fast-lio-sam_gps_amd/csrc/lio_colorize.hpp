@@ -7,16 +7,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-namespace lio {
+#include "lio_camera.hpp"
 
-// What a kernel needs of one frame's camera and pose: 16 + 12 doubles and the image size, passed by value.
-struct CamArg {
-    double fx, fy, cx, cy;
-    double k1, k2, p1, p2, k3, k4, k5, k6;
-    double r2_max;
-    double R[9], t[3];
-    int32_t width, height;
-};
+namespace lio {
 
 constexpr int kCzMaxSplat = 8;               // the largest splat radius
 constexpr uint32_t kCzInfBits = 0x7f800000u;  // bits of float +inf: an empty depth pixel
@@ -24,21 +17,10 @@ constexpr uint32_t kCzInfBits = 0x7f800000u;  // bits of float +inf: an empty de
 // stages of colorizer_add_frame, for ColorizeBuf::ms (event times of the last frame)
 enum CzStage { kCzUpload = 0, kCzFill = 1, kCzSplat = 2, kCzResolve = 3, kCzStages = 4 };
 
-// scratch of lio_project_points on a lio_filter: one arena for the four outputs
-struct ProjectBuf {
-    void* arena = nullptr;
-    size_t arena_bytes = 0;
-};
-void project_free(ProjectBuf& b);
-
 // records (device, n x stride) -> uv (n x 2 doubles), zc (n doubles), pix (n x 2 int32, -1 where invalid), valid
 // (n uint8), each to the HOST pointer given (uv / zc / pix may be null).  Waits for the stream.
 int project_points(ProjectBuf& b, const float* d_pts, int64_t n, int stride, const CamArg& cam, double* uv_opt,
                    double* zc_opt, int32_t* pix_opt, uint8_t* valid, hipStream_t st);
-
-// pinned host memory of at least `need` bytes, grown geometrically and counted (lio_alloc_count): the image staging
-// of the colorizer and of the undistorter
-int grow_pinned(uint8_t** p, size_t& bytes, size_t need);
 
 // the state of a lio_colorizer: the cloud and the per-point state stay on the device between frames
 struct ColorizeBuf {

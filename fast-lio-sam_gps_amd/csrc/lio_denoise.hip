@@ -484,9 +484,8 @@ int dn_build_grid(DenoiseBuf& b, const float* d_pts, int64_t n, int stride, floa
 }
 
 void denoise_free(DenoiseBuf& b) {
-    if (b.arena) (void)hipFree(b.arena);
-    if (b.h_dist) (void)hipHostFree(b.h_dist);
-    if (b.h_cnt) (void)hipHostFree(b.h_cnt);
+    dev_free(&b.arena);
+    host_free(&b.h_dist, &b.h_cnt);
     b = DenoiseBuf{};
 }
 
@@ -495,8 +494,8 @@ int denoise_reserve(DenoiseBuf& b, int64_t n) {
     if (n <= b.cap && b.arena) return kOk;
     const int64_t c = std::min<int64_t>(grown<int64_t>(n, b.cap, 4096), 0x7fffff00);
     dev_free(&b.arena);
-    if (b.h_dist) (void)hipHostFree(b.h_dist);
-    b.h_dist = nullptr, b.cap = 0;
+    host_free(&b.h_dist);
+    b.arena_bytes = 0, b.h_dist_bytes = 0, b.cap = 0;
     if (!b.h_cnt) {
         count_alloc();
         if (hipHostMalloc(&b.h_cnt, 64) != hipSuccess) return kNoMem;
@@ -508,25 +507,21 @@ int denoise_reserve(DenoiseBuf& b, int64_t n) {
     LIO_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, sx, b.flags, b.pos, (int)(c + 1)));
     const size_t tmp = std::max(std::max(s32, s64), sx) + 256;
     const size_t C = (size_t)c;
-    auto carve = [&](Carver at) {  // the arena's fields, once each, in arena order
+    auto fields = [&](Carver& at) {  // the arena's fields, once each, in arena order
         at(b.keys, C), at(b.keys_alt, C), at(b.vals, C), at(b.vals_alt, C);
         at(b.start, C + 66), at(b.g4, C), at(b.part, 6 * kDnPartBlocks), at(b.geom, 1);
         at(b.dist, C), at(b.flags, C + 1), at(b.pos, C + 1);
         at(b.seeds_xyz, 3 * C), at(b.seed_id, C), at(b.seed_d2, C), at(b.idx, C), at(b.idx_alt, C);
         at(b.k64, C), at(b.k64_alt, C), at(b.cloud_a, 4 * C), at(b.cloud_b, 4 * C), at(b.tmp, tmp);
-        return at.bytes();
     };
-    const size_t total = carve(Carver{});
-    count_alloc(2);
-    if (hipMalloc(&b.arena, total) != hipSuccess || hipHostMalloc(&b.h_dist, C * sizeof(float)) != hipSuccess) {
+    int rc = reserve_arena(&b.arena, b.arena_bytes, fields, 0);
+    if (!rc) rc = grow_pinned(&b.h_dist, b.h_dist_bytes, C * sizeof(float), 0);  // exactly the capacity, with the arena
+    if (rc) {
         dev_free(&b.arena);
-        b.h_dist = nullptr;
-        return kNoMem;
+        b.arena_bytes = 0;
+        return rc;
     }
-    carve(Carver{b.arena});
-    b.arena_bytes = total;
     b.tmp_bytes = tmp;
-    b.h_cap = c;
     b.cap = c;
     return kOk;
 }

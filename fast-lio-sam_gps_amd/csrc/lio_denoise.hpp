@@ -41,8 +41,8 @@ struct DenoiseBuf {
     float *cloud_a = nullptr, *cloud_b = nullptr;  // 4 cap each
     void* tmp = nullptr;         // hipcub scratch
     size_t tmp_bytes = 0;
-    float* h_dist = nullptr;     // pinned, h_cap floats
-    int64_t h_cap = 0;
+    float* h_dist = nullptr;     // pinned, cap floats
+    size_t h_dist_bytes = 0;
     uint32_t* h_cnt = nullptr;   // pinned: compaction counts
 };
 

@@ -743,8 +743,7 @@ int records_to_xyz(const float* d_rec, int64_t n, int stride, float* d_xyz, hipS
 void filter_free(FilterBuf& b) {
     dev_free(&b.keys, &b.keys_alt, &b.vals, &b.vals_alt, &b.head, &b.vid, &b.part, &b.geom, &b.tmp, &b.a, &b.c, &b.aux,
              &b.cnt);
-    if (b.h_small) (void)hipHostFree(b.h_small);
-    if (b.h_stage) (void)hipHostFree(b.h_stage);
+    host_free(&b.h_small, &b.h_stage);
     b = FilterBuf{};
 }
 

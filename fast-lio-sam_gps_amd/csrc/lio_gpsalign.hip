@@ -247,26 +247,9 @@ int ga_reserve(GpsAlignBuf& g, int64_t n, int64_t m, int64_t nchunks) {
         c(g.part_k, (size_t)(nchunks * n));
         c(g.part, (size_t)(kGaMaxSums * nb));
     };
-    Carver measure;
-    fields(measure);
-    int rc = grow_scratch(&g.arena, g.arena_bytes, measure.bytes());
+    const int rc = reserve_arena(&g.arena, g.arena_bytes, fields);
     if (rc) return rc;
-    Carver assign(g.arena);
-    fields(assign);
-    const size_t hb = (size_t)(kGaMaxSums * nb) * sizeof(double);
-    if (hb > g.h_bytes || !g.h_part) {
-        if (g.h_part) (void)hipHostFree(g.h_part);
-        g.h_part = nullptr;
-        const size_t c = grown(hb, g.h_bytes, (size_t)1 << 16);
-        g.h_bytes = 0;
-        count_alloc();
-        if (hipHostMalloc(reinterpret_cast<void**>(&g.h_part), c) != hipSuccess) {
-            g.h_part = nullptr;
-            return kNoMem;
-        }
-        g.h_bytes = c;
-    }
-    return kOk;
+    return grow_pinned(&g.h_part, g.h_bytes, (size_t)(kGaMaxSums * nb) * sizeof(double), (size_t)1 << 16);
 }
 
 // the block sums of k TREEs to the host, each added in ascending block order from 0.0
@@ -325,7 +308,7 @@ int64_t ga_chunk_width(int64_t n, int64_t m) {
 
 void gps_align_free(GpsAlignBuf& g) {
     dev_free(&g.arena, &g.geo_xy);
-    if (g.h_part) (void)hipHostFree(g.h_part);
+    host_free(&g.h_part);
     g = GpsAlignBuf{};
 }
 

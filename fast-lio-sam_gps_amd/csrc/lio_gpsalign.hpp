@@ -17,7 +17,7 @@ constexpr int64_t kGaMaxChunks = 32;
 constexpr int64_t kGaWantGroups = 2048;  // workgroups aimed at: 8 per CU
 int64_t ga_chunk_width(int64_t n, int64_t m);
 
-// offsets into the result array of gps_align: the values of LIO_GPSALIGN_* (lio_capi.cpp asserts it)
+// offsets into the result array of gps_align: the values of LIO_GPSALIGN_* (lio_capi_post.cpp asserts it)
 enum GaOut {
     kGaIters = 0, kGaConverged = 1, kGaMeanError = 2, kGaS0 = 3, kGaCA = 4, kGaCB = 6, kGaSc = 8, kGaC = 9, kGaS = 10,
     kGaT = 11, kGaCD = 13, kGaRefScale = 15, kGaRefC = 16, kGaRefS = 17, kGaRefT = 18, kGaTotScale = 20, kGaTotC = 21,

@@ -260,7 +260,7 @@ __global__ void insert_clear_kernel(uint32_t* __restrict__ addc, const uint32_t*
 void grid_free(GridBuf& g) {
     dev_free(&g.pts, &g.by_id, &g.start, &g.keys, &g.keys_alt, &g.vals, &g.vals_alt, &g.tmp, &g.aabb, &g.xyz, &g.ckeys,
              &g.rng, &g.lim, &g.addc, &g.dirty, &g.bump);
-    if (g.aabb_host) (void)hipHostFree(g.aabb_host);
+    host_free(&g.aabb_host);
     const bool gapped = g.gapped;
     g = GridBuf{};
     g.gapped = gapped;

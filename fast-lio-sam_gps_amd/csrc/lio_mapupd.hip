@@ -1184,7 +1184,7 @@ void mapupd_free(MapUpdBuf& u) {
     dev_free(&u.f64, &u.pos64, &u.add_flag, &u.pos, &u.cls, &u.world, &u.xyz_a, &u.xyz_b, &u.pending, &u.skey, &u.sval,
              &u.skey2, &u.sval2, &u.xs, &u.vlist, &u.dlist, &u.tmp_cell, &u.tmp_rank, &u.tlist, &u.hkey, &u.hhead, &u.hend,
              &u.tmp, &u.cnt, &u.boxes, &u.vnruns, &u.runs, &u.blk);
-    if (u.h_cnt) (void)hipHostFree(u.h_cnt);
+    host_free(&u.h_cnt);
     u = MapUpdBuf{};
 }
 

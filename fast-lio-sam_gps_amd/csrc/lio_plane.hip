@@ -215,20 +215,14 @@ int plane_reserve(PlaneBuf& p, int64_t n, int64_t K) {
     const int64_t cn = n <= p.cap_n ? p.cap_n : grown<int64_t>(n, p.cap_n, 4096);
     const int64_t ck = K <= p.cap_k ? p.cap_k : grown<int64_t>(K, p.cap_k, 1024);
     dev_free(&p.arena);
-    p.cap_n = 0, p.cap_k = 0;
+    p.arena_bytes = 0, p.cap_n = 0, p.cap_k = 0;
     const size_t N = (size_t)cn, H = (size_t)ck;
-    auto carve = [&](Carver at) {  // the arena's fields, once each, in arena order
+    auto fields = [&](Carver& at) {  // the arena's fields, once each, in arena order
         at(p.planes, H), at(p.cnt, H), at(p.sq, H), at(p.mask, N), at(p.inliers, N);
         at(p.part, 9 * kMomBlocks), at(p.mom, 10), at(p.win, 1);
-        return at.bytes();
     };
-    const size_t total = carve(Carver{});
-    count_alloc();
-    if (hipMalloc(&p.arena, total) != hipSuccess) {
-        p.arena = nullptr;
-        return kNoMem;
-    }
-    carve(Carver{p.arena});
+    const int rc = reserve_arena(&p.arena, p.arena_bytes, fields, 0);
+    if (rc) return rc;
     p.cap_n = cn, p.cap_k = ck;
     return kOk;
 }
@@ -293,7 +287,7 @@ inline uint64_t mix64(uint64_t z) {  // splitmix64's output function
 
 void plane_free(PlaneBuf& p) {
     dev_free(&p.arena);
-    if (p.h_pin) (void)hipHostFree(p.h_pin);
+    host_free(&p.h_pin);
     p = PlaneBuf{};
 }
 

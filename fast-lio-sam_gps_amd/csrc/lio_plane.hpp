@@ -23,6 +23,7 @@ struct PlaneWinner {  // written by the selection kernel
 // a small pinned block.  5 bytes per point, 32 bytes per hypothesis.
 struct PlaneBuf {
     void* arena = nullptr;
+    size_t arena_bytes = 0;
     int64_t cap_n = 0, cap_k = 0;
     float4* planes = nullptr;            // per hypothesis (a, b, c, d); NaN when degenerate
     unsigned long long* cnt = nullptr;   // per hypothesis: inliers

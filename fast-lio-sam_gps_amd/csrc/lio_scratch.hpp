@@ -1,6 +1,12 @@
-// lio_scratch.hpp — the host-side plumbing every scratch struct shares (FilterBuf, GridBuf, MapUpdBuf,
-// DenoiseBuf, ClusterBuf, PlaneBuf): status codes, the arena carver, the HIP check, nblk(), the device-buffer
-// growth and free helpers.  The hipcub sort / scan pair is in lio_scratch_cub.hpp.  Host only, header only.
+// lio_scratch.hpp — the host-side plumbing every scratch struct shares.  Host only, header only.
+//   status codes, LIO_HIP, nblk(), grown()          every driver
+//   Carver, carve_arena, reserve_arena              the one-arena reserves: DenoiseBuf, ClusterBuf, PlaneBuf (sized by a
+//                                                   capacity the caller keeps), GpsAlignBuf, ProjectBuf (sized per call)
+//   dev_free, dev_alloc_all, grow_buf, grow_scratch device buffers: FilterBuf, GridBuf, MapUpdBuf, ColorizeBuf,
+//                                                   UndistortBuf and the C-ABI's handles
+//   host_free, grow_pinned                          pinned host buffers: the sweep staging (FilterBuf), the image staging
+//                                                   (ColorizeBuf, UndistortBuf), GpsAlignBuf::h_part, DenoiseBuf::h_dist
+// The hipcub sort / scan pair is in lio_scratch_cub.hpp.
 //
 // The first section needs no HIP header: define LIO_SCRATCH_NO_HIP before the include to get it alone
 // (tests/cpp/scratch_layout.cpp does).
@@ -11,12 +17,12 @@
 namespace lio {
 
 // status of the internal drivers; the values of LIO_OK, LIO_ERR_ARG, LIO_ERR_HIP and LIO_ERR_NOMEM
-// (lio_capi.cpp asserts it and turns them into the public code and message)
+// (lio_capi_util.hpp asserts it and turns them into the public code and message)
 constexpr int kOk = 0, kArg = -1, kHip = -2, kNoMem = -5;
 
-// Carves one arena into 256-byte-aligned slots.  A reserve lists its fields ONCE, in a function of a Carver,
-// and runs that function twice: over Carver{} to measure (every field is set to null, bytes() is the arena
-// size), then over Carver{arena} to assign.  A zero-count field takes no space.
+// Carves one arena into 256-byte-aligned slots.  A reserve lists its fields ONCE, in a function of a Carver&,
+// and carve_arena runs that function twice: over Carver{} to measure (every field is set to null, bytes() is
+// the arena size), then over Carver{arena} to assign.  A zero-count field takes no space.
 class Carver {
 public:
     explicit Carver(void* base = nullptr) : base_(static_cast<uint8_t*>(base)) {}
@@ -37,6 +43,20 @@ private:
     size_t off_ = 0;
 };
 
+// The two passes of a reserve.  fields(Carver&) lists every field once; alloc(bytes) returns a block of at least
+// the measured size, or null when it cannot: the fields then stay null.  Returns where the assign pass ends,
+// which is the measured size.
+template <class Fields, class Alloc>
+size_t carve_arena(Fields&& fields, Alloc&& alloc) {
+    Carver measure;
+    fields(measure);
+    void* block = alloc(measure.bytes());
+    if (!block) return measure.bytes();
+    Carver assign(block);
+    fields(assign);
+    return assign.bytes();
+}
+
 }  // namespace lio
 
 #ifndef LIO_SCRATCH_NO_HIP
@@ -49,7 +69,7 @@ private:
 #include "lio_error.hpp"
 
 // A failed HIP call leaves "<call>: <hipGetErrorString>" in last_error() and returns kHip; the C-ABI's status
-// message appends that text (lio_capi.cpp status()).
+// message appends that text (lio_capi_util.hpp status()).
 #define LIO_HIP(x)                                                                      \
     do {                                                                                \
         const hipError_t e_ = (x);                                                      \
@@ -73,6 +93,12 @@ N grown(N need, N cap, N floor = 0) {
 template <class... T>
 void dev_free(T**... p) {
     ((*p ? (void)hipFree(*p) : (void)0, *p = nullptr), ...);
+}
+
+// hipHostFree and null every pointer given (null ones are skipped)
+template <class... T>
+void host_free(T**... p) {
+    ((*p ? (void)hipHostFree(*p) : (void)0, *p = nullptr), ...);
 }
 
 // One device buffer of a multi-buffer reserve: dev_alloc_all({dev_req(b.keys, c), dev_req(b.head, c + 1), ...})
@@ -122,6 +148,36 @@ inline int grow_scratch(void** p, size_t& bytes, size_t need, size_t floor = (si
     const int rc = dev_alloc_all({{p, c}});
     if (rc == kOk) bytes = c;
     return rc;
+}
+
+// carve_arena over *arena, which grow_scratch keeps at least as large as the fields measure (`bytes` is its size).
+// A reserve with a capacity policy of its own measures its capacity, not the call: it frees *arena and zeroes
+// `bytes` first and passes floor 0, and the arena is then exactly the measured size.
+template <class Fields>
+int reserve_arena(void** arena, size_t& bytes, Fields&& fields, size_t floor = (size_t)1 << 20) {
+    int rc = kOk;
+    carve_arena(fields, [&](size_t need) -> void* {
+        rc = grow_scratch(arena, bytes, need, floor);
+        return rc ? nullptr : *arena;
+    });
+    return rc;
+}
+
+// pinned host memory: *p holds at least `need` bytes (contents are not kept across a growth), grown as grow_buf
+// grows and counted (lio_alloc_count).  kNoMem leaves *p null and bytes 0.
+template <class T>
+int grow_pinned(T** p, size_t& bytes, size_t need, size_t floor) {
+    if (need <= bytes && *p) return kOk;
+    const size_t c = grown(need, bytes, floor);
+    host_free(p);
+    bytes = 0;
+    count_alloc();
+    if (hipHostMalloc(reinterpret_cast<void**>(p), c, hipHostMallocDefault) != hipSuccess) {
+        *p = nullptr;
+        return kNoMem;
+    }
+    bytes = c;
+    return kOk;
 }
 
 }  // namespace lio

@@ -155,17 +155,13 @@ int undistort_map(ProjectBuf& b, const CamArg& src, const UdDst& dst, double* uv
     double2* d_uv = nullptr;
     int2* d_sxy = nullptr;
     uchar2* d_axy = nullptr;
-    auto carve = [&](Carver& c) {
+    auto fields = [&](Carver& c) {
         c(d_uv, uv_opt ? n : 0);
         c(d_sxy, sxy_opt ? n : 0);
         c(d_axy, axy_opt ? n : 0);
     };
-    Carver measure;
-    carve(measure);
-    int rc = grow_scratch(&b.arena, b.arena_bytes, measure.bytes());
+    int rc = reserve_arena(&b.arena, b.arena_bytes, fields);
     if (rc) return rc;
-    Carver assign(b.arena);
-    carve(assign);
     if (!uv_opt) d_uv = nullptr;
     if (!sxy_opt) d_sxy = nullptr;
     if (!axy_opt) d_axy = nullptr;
@@ -184,8 +180,7 @@ int undistorter_init(UndistortBuf& u) {
 
 void undistorter_free(UndistortBuf& u) {
     dev_free(&u.map, &u.img, &u.out);
-    if (u.h_img) (void)hipHostFree(u.h_img);
-    if (u.h_out) (void)hipHostFree(u.h_out);
+    host_free(&u.h_img, &u.h_out);
     for (hipEvent_t e : u.ev)
         if (e) (void)hipEventDestroy(e);
     u = UndistortBuf{};
@@ -213,8 +208,8 @@ int undistorter_run(UndistortBuf& u, const uint8_t* image, int64_t pitch, uint8_
     const size_t row_bytes = (size_t)u.dw * (size_t)C;
     const int64_t d_pitch = (int64_t)((row_bytes + 3) & ~(size_t)3);
     const size_t out_bytes = (size_t)d_pitch * (size_t)u.dh;
-    int rc = grow_pinned(&u.h_img, u.h_img_bytes, in_bytes);
-    if (!rc) rc = grow_pinned(&u.h_out, u.h_out_bytes, out_bytes);
+    int rc = grow_pinned(&u.h_img, u.h_img_bytes, in_bytes, kImageStageFloor);
+    if (!rc) rc = grow_pinned(&u.h_out, u.h_out_bytes, out_bytes, kImageStageFloor);
     if (!rc) rc = grow_scratch(reinterpret_cast<void**>(&u.img), u.img_bytes, in_bytes);
     if (!rc) rc = grow_scratch(reinterpret_cast<void**>(&u.out), u.out_bytes, out_bytes);
     if (rc) return rc;

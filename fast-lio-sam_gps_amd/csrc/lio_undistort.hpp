@@ -6,7 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "lio_colorize.hpp"
+#include "lio_camera.hpp"
 
 namespace lio {
 

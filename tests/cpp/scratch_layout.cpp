@@ -1,7 +1,8 @@
 // scratch_layout.cpp — the arena carver of csrc/lio_scratch.hpp on the host alone (no HIP, no GPU): one field
-// list run twice, over Carver{} to measure and over Carver{block} to assign, as the filter handle's reserves
-// run it.  Built with -fsanitize=address,undefined by tests/test_scratch_layout.py: a slot that overlaps its
-// neighbour or leaves the block is a failed check here and a sanitizer report on the writes.
+// list run twice, over Carver{} to measure and over Carver{block} to assign, first by hand and then through
+// carve_arena, the helper every reserve runs (with aligned_alloc where the reserves grow a device arena).
+// Built with -fsanitize=address,undefined by tests/test_scratch_layout.py: a slot that overlaps its neighbour
+// or leaves the block is a failed check here and a sanitizer report on the writes.
 #define LIO_SCRATCH_NO_HIP
 #include "../../fast-lio-sam_gps_amd/csrc/lio_scratch.hpp"
 
@@ -26,8 +27,12 @@ struct Mixed {  // element sizes 1, 4, 8, 16 and a byte block, as the DenoiseBuf
     void* tmp = nullptr;       // 3 n + 7 bytes
 };
 
-size_t carve(Mixed& m, size_t n, lio::Carver at) {
+void fields(Mixed& m, size_t n, lio::Carver& at) {
     at(m.mask, n), at(m.keys, n), at(m.none, 0), at(m.mom, n), at(m.pts, n), at(m.head, n + 1), at(m.tmp, 3 * n + 7);
+}
+
+size_t carve(Mixed& m, size_t n, lio::Carver at) {
+    fields(m, n, at);
     return at.bytes();
 }
 
@@ -80,6 +85,33 @@ void run(size_t n) {
         CHECK(m.mask[0] == 0xa5 || n == 1);
         CHECK(m.mask[n - 1] == 0x5a && m.keys[n - 1] == 0x5a5a5a5au && m.head[n] == 0x5a5a5a5au);
     }
+
+    // the same list through carve_arena: it asks for the measured size once, ends where the hand-run assign pass
+    // ends, and puts every field where the hand-run two passes put it
+    Mixed h;
+    size_t asked = 0, calls = 0;
+    uint8_t* hblock = nullptr;
+    const size_t end = lio::carve_arena([&](lio::Carver& at) { fields(h, n, at); },
+                                        [&](size_t bytes) -> void* {
+                                            asked = bytes, ++calls;
+                                            return hblock = static_cast<uint8_t*>(std::aligned_alloc(256, bytes));
+                                        });
+    CHECK(calls == 1 && asked == total && end == total);
+    CHECK(hblock != nullptr);
+    if (hblock) {
+        auto same = [&](const void* a, const void* b) {
+            return static_cast<const uint8_t*>(a) - hblock == static_cast<const uint8_t*>(b) - block;
+        };
+        CHECK(same(h.mask, m.mask) && same(h.keys, m.keys) && same(h.none, m.none) && same(h.mom, m.mom));
+        CHECK(same(h.pts, m.pts) && same(h.head, m.head) && same(h.tmp, m.tmp));
+        touch(h.mask, n), touch(h.keys, n), touch(h.mom, n), touch(h.pts, n), touch(h.head, n + 1);
+        touch(static_cast<uint8_t*>(h.tmp), 3 * n + 7);
+        std::free(hblock);
+    }
+    // an allocation that fails leaves every field null and still reports the measured size
+    Mixed z;
+    CHECK(lio::carve_arena([&](lio::Carver& at) { fields(z, n, at); }, [](size_t) -> void* { return nullptr; }) == total);
+    CHECK(!z.mask && !z.keys && !z.none && !z.mom && !z.pts && !z.head && !z.tmp);
     std::free(block);
 }
 

@@ -1,6 +1,7 @@
 """The arena carver of csrc/lio_scratch.hpp, host only: tests/cpp/scratch_layout.cpp carves a struct of mixed
 element types for counts 0, 1, 255, 257 and 4097 and checks sizes, 256-byte alignment, no overlap, zero-count
-fields and the first / last element of every field, built with the address and undefined-behaviour sanitizers
+fields and the first / last element of every field, by hand and through carve_arena (the measure / assign helper
+every reserve runs), built with the address and undefined-behaviour sanitizers
 (a stand-alone program: nothing is preloaded)."""
 import os
 import subprocess
