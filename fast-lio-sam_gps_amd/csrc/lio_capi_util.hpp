@@ -1,16 +1,12 @@
-// lio_capi_util.hpp — what every file of the C-ABI (include/lio_gpu.h) shares: the error reporting, the device
-// check, the public code of an internal status, the handle shell, the filter handle and the tails its entry
-// points have in common.  Private to lio_capi.cpp (map, ctx, match, IESKF, filters, preprocessing, formats),
+// lio_capi_util.hpp — what every file of the C-ABI (include/lio_gpu.h) shares: the error reporting and the device
+// check (lio_capi_base.hpp), the public code of an internal status, the handle shell, the filter handle and the
+// tails its entry points have in common.  Private to lio_capi.cpp (map, ctx, match, IESKF, filters, preprocessing, formats),
 // lio_capi_post.cpp (the offline leg on a lio_filter) and lio_capi_camera.cpp (the camera leg); each says
 // `using namespace lio::capi`.  The functions are static: each file has its own and the library exports none.
 #pragma once
-#include "../../include/lio_gpu.h"
-
-#include <hip/hip_runtime.h>
+#include "lio_capi_base.hpp"  // fail, HIP_TRY, check_device (shared with the loop-ICP files)
 
 #include <cmath>
-#include <cstring>
-#include <string>
 
 #include "lio_camera.hpp"
 #include "lio_cluster.hpp"
@@ -23,29 +19,6 @@
 #include "lio_scratch.hpp"
 
 namespace lio::capi {
-
-static inline int fail(int code, const std::string& msg) {
-    lio::last_error() = msg;
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                           \
-    do {                                                                                        \
-        hipError_t e_ = (expr);                                                                 \
-        if (e_ != hipSuccess) return fail(LIO_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-static inline int check_device(int dev) {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
-        return fail(LIO_ERR_NODEV, "no HIP device visible (this library has no CPU path)");
-    if (dev < 0 || dev >= n) return fail(LIO_ERR_ARG, "device ordinal out of range");
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return fail(LIO_ERR_HIP, "hipGetDeviceProperties failed");
-    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        return fail(LIO_ERR_NODEV, std::string("built for gfx950, device is ") + prop.gcnArchName);
-    return LIO_OK;
-}
 
 static_assert(lio::kOk == LIO_OK && lio::kArg == LIO_ERR_ARG && lio::kHip == LIO_ERR_HIP && lio::kNoMem == LIO_ERR_NOMEM,
               "the internal status codes are the public ones");

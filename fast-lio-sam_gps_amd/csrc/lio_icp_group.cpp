@@ -32,15 +32,12 @@
 #include <vector>
 
 #include "../../include/lio_gpu.h"
-#include "lio_error.hpp"
+#include "lio_capi_base.hpp"
 #include "lio_rccl.hpp"
 
-namespace {
+using lio::capi::fail;
 
-int gfail(int code, const std::string& msg) {
-    lio::last_error() = msg;
-    return code;
-}
+namespace {
 
 using lio::kNcclDouble;
 using lio::ncclComm_t;
@@ -142,9 +139,9 @@ int rccl_warmup(lio_icp_group* g) {
     int rc = LIO_OK;
     for (int r = 0; r < n && rc == LIO_OK; ++r) {
         if (hipSetDevice(g->dev[r]) != hipSuccess || hipMalloc(&buf[r], (size_t)(n + 1) * sizeof(double)) != hipSuccess)
-            rc = gfail(LIO_ERR_NOMEM, "lio_icp_group_create: warm-up buffers");
+            rc = fail(LIO_ERR_NOMEM, "lio_icp_group_create: warm-up buffers");
         else if (hipMemset(buf[r], 0, (size_t)(n + 1) * sizeof(double)) != hipSuccess)
-            rc = gfail(LIO_ERR_HIP, "lio_icp_group_create: warm-up buffers");
+            rc = fail(LIO_ERR_HIP, "lio_icp_group_create: warm-up buffers");
     }
     if (rc == LIO_OK) {
         ncclResult_t nr = g->rccl.GroupStart();
@@ -152,12 +149,12 @@ int rccl_warmup(lio_icp_group* g) {
             nr = g->rccl.AllGather(buf[r] + n, buf[r], 1, kNcclDouble, g->comms[r], nullptr);
         const ncclResult_t ne = g->rccl.GroupEnd();
         if (nr == 0) nr = ne;
-        if (nr != 0) rc = gfail(LIO_ERR_STATE, std::string("RCCL warm-up all-gather: ") + g->rccl.GetErrorString(nr));
+        if (nr != 0) rc = fail(LIO_ERR_STATE, std::string("RCCL warm-up all-gather: ") + g->rccl.GetErrorString(nr));
     }
     for (int r = 0; r < n; ++r) {
         if (!buf[r]) continue;
         (void)hipSetDevice(g->dev[r]);
-        if (hipDeviceSynchronize() != hipSuccess && rc == LIO_OK) rc = gfail(LIO_ERR_HIP, "RCCL warm-up: device error");
+        if (hipDeviceSynchronize() != hipSuccess && rc == LIO_OK) rc = fail(LIO_ERR_HIP, "RCCL warm-up: device error");
         (void)hipFree(buf[r]);
     }
     return rc;
@@ -168,11 +165,11 @@ int rccl_warmup(lio_icp_group* g) {
 extern "C" {
 
 int lio_icp_group_create(const lio_icp_params* p, int n_gpus, const int* devices, lio_icp_group** out) {
-    if (!p || !out || n_gpus < 1 || n_gpus > 64) return gfail(LIO_ERR_ARG, "lio_icp_group_create: bad arguments");
+    if (!p || !out || n_gpus < 1 || n_gpus > 64) return fail(LIO_ERR_ARG, "lio_icp_group_create: bad arguments");
     *out = nullptr;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return gfail(LIO_ERR_NODEV, "lio_icp_group_create: no HIP device (no CPU path)");
+        return fail(LIO_ERR_NODEV, "lio_icp_group_create: no HIP device (no CPU path)");
     auto* g = new lio_icp_group();
     g->world = n_gpus;
     g->dev.resize(n_gpus);
@@ -200,13 +197,13 @@ int lio_icp_group_create(const lio_icp_params* p, int n_gpus, const int* devices
     if (rc == LIO_OK && g->use_rccl) {
         std::string why;
         if (!lio::load_rccl(g->rccl, why)) {
-            rc = gfail(LIO_ERR_STATE, "lio_icp_group_create: " + why);
+            rc = fail(LIO_ERR_STATE, "lio_icp_group_create: " + why);
         } else {
             g->comms.assign(n_gpus, nullptr);
             const ncclResult_t nr = g->rccl.CommInitAll(g->comms.data(), n_gpus, g->dev.data());
             if (nr != 0) {
                 g->comms.clear();
-                rc = gfail(LIO_ERR_STATE, std::string("ncclCommInitAll: ") + g->rccl.GetErrorString(nr));
+                rc = fail(LIO_ERR_STATE, std::string("ncclCommInitAll: ") + g->rccl.GetErrorString(nr));
             } else {
                 rc = rccl_warmup(g);
             }
@@ -233,7 +230,7 @@ int lio_icp_group_size(const lio_icp_group* g) { return g ? g->world : 0; }
 int lio_icp_group_uses_rccl(const lio_icp_group* g) { return g && g->use_rccl ? 1 : 0; }
 
 int lio_icp_group_set_target(lio_icp_group* g, const float* xyz, int64_t n) {
-    if (!g) return gfail(LIO_ERR_ARG, "lio_icp_group_set_target: NULL group");
+    if (!g) return fail(LIO_ERR_ARG, "lio_icp_group_set_target: NULL group");
     for (lio_icp* h : g->h) {  // replicated on every device
         const int rc = lio_icp_set_target(h, xyz, n);
         if (rc) return rc;
@@ -242,7 +239,7 @@ int lio_icp_group_set_target(lio_icp_group* g, const float* xyz, int64_t n) {
 }
 
 int lio_icp_group_set_source(lio_icp_group* g, const float* xyz, int64_t n) {
-    if (!g) return gfail(LIO_ERR_ARG, "lio_icp_group_set_source: NULL group");
+    if (!g) return fail(LIO_ERR_ARG, "lio_icp_group_set_source: NULL group");
     for (lio_icp* h : g->h) {  // each handle keeps the full source on the host and uploads its shard
         const int rc = lio_icp_set_source(h, xyz, n);
         if (rc) return rc;
@@ -252,11 +249,11 @@ int lio_icp_group_set_source(lio_icp_group* g, const float* xyz, int64_t n) {
 }
 
 int lio_icp_group_align(lio_icp_group* g, const float* guess16, lio_icp_result* out, float* aligned_opt) {
-    if (!g || !out) return gfail(LIO_ERR_ARG, "lio_icp_group_align: bad arguments");
+    if (!g || !out) return fail(LIO_ERR_ARG, "lio_icp_group_align: bad arguments");
     if (g->world == 1) return lio_icp_align(g->h[0], guess16, out, aligned_opt);
     {
         std::lock_guard<std::mutex> lk(g->mu);
-        if (g->failed) return gfail(LIO_ERR_STATE, "lio_icp_group_align: the group failed earlier (recreate it)");
+        if (g->failed) return fail(LIO_ERR_STATE, "lio_icp_group_align: the group failed earlier (recreate it)");
         g->arrived = 0;
     }
     std::vector<lio_icp_result> res(g->world);
@@ -275,10 +272,10 @@ int lio_icp_group_align(lio_icp_group* g, const float* guess16, lio_icp_result* 
         });
     for (std::thread& t : th) t.join();
     for (int r = 0; r < g->world; ++r)
-        if (rcs[r] != LIO_OK) return gfail(rcs[r], "lio_icp_group_align: rank " + std::to_string(r) + ": " + errs[r]);
+        if (rcs[r] != LIO_OK) return fail(rcs[r], "lio_icp_group_align: rank " + std::to_string(r) + ": " + errs[r]);
     for (int r = 1; r < g->world; ++r)  // every rank summed the same records in the same order
         if (std::memcmp(res[r].T, res[0].T, sizeof(res[0].T)) != 0 || res[r].iterations != res[0].iterations)
-            return gfail(LIO_ERR_STATE, "lio_icp_group_align: ranks disagree (not bit-identical)");
+            return fail(LIO_ERR_STATE, "lio_icp_group_align: ranks disagree (not bit-identical)");
     *out = res[0];
     return LIO_OK;
 }

@@ -25,18 +25,15 @@
 #include <string>
 
 #include "../../include/lio_gpu.h"
-#include "lio_error.hpp"
+#include "lio_capi_base.hpp"
 #include "lio_rccl.hpp"
+
+using lio::capi::fail;
 
 extern "C" void lio_icp_set_exchange_owner(lio_icp* h, void* owner, void (*free_fn)(void*));
 extern "C" int lio_icp_device(const lio_icp* h);
 
 namespace {
-
-int mfail(int code, const std::string& msg) {
-    lio::last_error() = msg;
-    return code;
-}
 
 // ------------------------------------------------------------------ shared-memory all-gather
 constexpr uint32_t kShmMagic = 0x4c494f58u;  // rank 0 has written world / n
@@ -94,7 +91,7 @@ void shm_close(ShmEx* e) {
 // attach completes the world unlinks the name at once, so no later close can remove a newer segment that
 // reuses it.
 int shm_open_ex(const char* name, int rank, int world, int64_t n, ShmEx** out) {
-    if (!name || name[0] != '/' || rank < 0 || rank >= world || n < 1) return mfail(LIO_ERR_ARG, "lio_shm_exchange_open: bad arguments");
+    if (!name || name[0] != '/' || rank < 0 || rank >= world || n < 1) return fail(LIO_ERR_ARG, "lio_shm_exchange_open: bad arguments");
     auto* e = new ShmEx();
     e->name = name;
     e->rank = rank;
@@ -123,7 +120,7 @@ int shm_open_ex(const char* name, int rank, int world, int64_t n, ShmEx** out) {
     if (fd < 0) {
         const std::string nm = name;
         delete e;
-        return mfail(LIO_ERR_STATE, "lio_shm_exchange_open: cannot open shared memory " + nm);
+        return fail(LIO_ERR_STATE, "lio_shm_exchange_open: cannot open shared memory " + nm);
     }
     struct stat sb;
     if (fstat(fd, &sb) == 0) e->ino = sb.st_ino;
@@ -131,7 +128,7 @@ int shm_open_ex(const char* name, int rank, int world, int64_t n, ShmEx** out) {
     close(fd);
     if (p == MAP_FAILED) {
         delete e;
-        return mfail(LIO_ERR_NOMEM, "lio_shm_exchange_open: mmap failed");
+        return fail(LIO_ERR_NOMEM, "lio_shm_exchange_open: mmap failed");
     }
     e->hdr = static_cast<ShmHdr*>(p);
     e->data = reinterpret_cast<double*>(static_cast<char*>(p) + sizeof(ShmHdr));
@@ -147,7 +144,7 @@ int shm_open_ex(const char* name, int rank, int world, int64_t n, ShmEx** out) {
                                     std::to_string(e->hdr->n) + ")";
             munmap(e->hdr, e->bytes);
             delete e;
-            return mfail(LIO_ERR_STATE, msg);
+            return fail(LIO_ERR_STATE, msg);
         }
     }
     if (e->hdr->attached.fetch_add(1, std::memory_order_acq_rel) + 1 == world) unlink_if_ours(e->name, e->ino);
@@ -186,13 +183,13 @@ bool shm_barrier(ShmEx* e) {
 // enough: a rank can only reuse a set after passing the next round's barrier, which every rank reaches
 // after it has read this round's set
 int shm_allgather(ShmEx* e, const double* send, int64_t n, double* recv) {
-    if (n > e->n) return mfail(LIO_ERR_ARG, "shared-memory exchange: more doubles than the segment holds");
+    if (n > e->n) return fail(LIO_ERR_ARG, "shared-memory exchange: more doubles than the segment holds");
     if (e->hdr->poisoned.load(std::memory_order_acquire))
-        return mfail(LIO_ERR_STATE, "shared-memory exchange: the segment is poisoned (an earlier barrier timed out)");
+        return fail(LIO_ERR_STATE, "shared-memory exchange: the segment is poisoned (an earlier barrier timed out)");
     double* set = e->data + (size_t)(e->round & 1) * (size_t)e->world * (size_t)e->n;
     std::memcpy(set + (size_t)e->rank * (size_t)e->n, send, (size_t)n * sizeof(double));
     if (!shm_barrier(e))
-        return mfail(LIO_ERR_STATE, "shared-memory exchange: a rank did not arrive in time (segment poisoned)");
+        return fail(LIO_ERR_STATE, "shared-memory exchange: a rank did not arrive in time (segment poisoned)");
     for (int r = 0; r < e->world; ++r)
         std::memcpy(recv + (size_t)r * (size_t)n, set + (size_t)r * (size_t)e->n, (size_t)n * sizeof(double));
     ++e->round;
@@ -231,7 +228,7 @@ int rccl_allgather_dev(const double* d_send, int64_t n, double* d_recv, void* st
 extern "C" {
 
 int lio_shm_exchange_open(const char* name, int rank, int world, int64_t n_per_rank, void** out) {
-    if (!out) return mfail(LIO_ERR_ARG, "lio_shm_exchange_open: out is NULL");
+    if (!out) return fail(LIO_ERR_ARG, "lio_shm_exchange_open: out is NULL");
     *out = nullptr;
     ShmEx* e = nullptr;
     const int rc = shm_open_ex(name, rank, world, n_per_rank, &e);
@@ -240,7 +237,7 @@ int lio_shm_exchange_open(const char* name, int rank, int world, int64_t n_per_r
 }
 
 int lio_shm_exchange_allgather(void* ex, const double* send, int64_t n, double* recv) {
-    if (!ex || !send || !recv || n < 0) return mfail(LIO_ERR_ARG, "lio_shm_exchange_allgather: bad arguments");
+    if (!ex || !send || !recv || n < 0) return fail(LIO_ERR_ARG, "lio_shm_exchange_allgather: bad arguments");
     return shm_allgather(static_cast<ShmEx*>(ex), send, n, recv);
 }
 
@@ -250,14 +247,14 @@ int lio_shm_exchange_close(void* ex) {
 }
 
 int lio_shm_exchange_set_timeout(void* ex, double seconds) {
-    if (!ex || !(seconds > 0.0)) return mfail(LIO_ERR_ARG, "lio_shm_exchange_set_timeout: bad arguments");
+    if (!ex || !(seconds > 0.0)) return fail(LIO_ERR_ARG, "lio_shm_exchange_set_timeout: bad arguments");
     static_cast<ShmEx*>(ex)->timeout_s = seconds;
     return LIO_OK;
 }
 
 int lio_icp_set_shard_shm(lio_icp* h, int rank, int world, const char* name, int64_t max_source_points) {
     if (!h || world < 1 || rank < 0 || rank >= world || max_source_points < 1)
-        return mfail(LIO_ERR_ARG, "lio_icp_set_shard_shm: bad arguments");
+        return fail(LIO_ERR_ARG, "lio_icp_set_shard_shm: bad arguments");
     if (world == 1) return lio_icp_set_shard(h, 0, 1, nullptr, nullptr);
     int64_t n = 0;
     int rc = lio_icp_exchange_len(max_source_points, world, &n);
@@ -275,30 +272,30 @@ int lio_icp_set_shard_shm(lio_icp* h, int rank, int world, const char* name, int
 }
 
 int lio_rccl_unique_id(uint8_t* id128) {
-    if (!id128) return mfail(LIO_ERR_ARG, "lio_rccl_unique_id: NULL");
+    if (!id128) return fail(LIO_ERR_ARG, "lio_rccl_unique_id: NULL");
     static lio::Rccl lib;
     static std::string why;
-    if (!lib.so && !lio::load_rccl(lib, why)) return mfail(LIO_ERR_STATE, "lio_rccl_unique_id: " + why);
+    if (!lib.so && !lio::load_rccl(lib, why)) return fail(LIO_ERR_STATE, "lio_rccl_unique_id: " + why);
     lio::ncclUniqueId u;
     const lio::ncclResult_t r = lib.GetUniqueId(&u);
-    if (r != 0) return mfail(LIO_ERR_STATE, std::string("ncclGetUniqueId: ") + lib.GetErrorString(r));
+    if (r != 0) return fail(LIO_ERR_STATE, std::string("ncclGetUniqueId: ") + lib.GetErrorString(r));
     std::memcpy(id128, u.internal, sizeof(u.internal));
     return LIO_OK;
 }
 
 int lio_icp_set_shard_rccl(lio_icp* h, int rank, int world, const uint8_t* id128) {
-    if (!h || !id128 || world < 1 || rank < 0 || rank >= world) return mfail(LIO_ERR_ARG, "lio_icp_set_shard_rccl: bad arguments");
+    if (!h || !id128 || world < 1 || rank < 0 || rank >= world) return fail(LIO_ERR_ARG, "lio_icp_set_shard_rccl: bad arguments");
     if (world == 1) return lio_icp_set_shard(h, 0, 1, nullptr, nullptr);
     auto* r = new RcclRank();
     std::string why;
     if (!lio::load_rccl(r->lib, why)) {
         delete r;
-        return mfail(LIO_ERR_STATE, "lio_icp_set_shard_rccl: " + why);
+        return fail(LIO_ERR_STATE, "lio_icp_set_shard_rccl: " + why);
     }
     r->dev = lio_icp_device(h);
     if (hipSetDevice(r->dev) != hipSuccess) {
         delete r;
-        return mfail(LIO_ERR_HIP, "lio_icp_set_shard_rccl: hipSetDevice");
+        return fail(LIO_ERR_HIP, "lio_icp_set_shard_rccl: hipSetDevice");
     }
     lio::ncclUniqueId u;
     std::memcpy(u.internal, id128, sizeof(u.internal));
@@ -307,7 +304,7 @@ int lio_icp_set_shard_rccl(lio_icp* h, int rank, int world, const uint8_t* id128
         const std::string msg = std::string("ncclCommInitRank: ") + r->lib.GetErrorString(nr);
         r->comm = nullptr;
         delete r;
-        return mfail(LIO_ERR_STATE, msg);
+        return fail(LIO_ERR_STATE, msg);
     }
     const int rc = lio_icp_set_shard_device(h, rank, world, rccl_allgather_dev, r);
     if (rc) {

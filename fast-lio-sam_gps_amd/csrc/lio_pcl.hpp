@@ -19,7 +19,7 @@ constexpr int kPclTicket = 20; // compaction block ticket (reset by the last blo
 constexpr int kPclOutWords = 24;  // pcl_pack output: 16 statistics, 2 status words, events (max over the means),
                                   // the compaction's time-out flag; sharded: [20] exchange flags (means | sigma << 8),
                                   // [21] / [22] the largest per-rank event list of the means / sigma chains; [23] the
-                                  // sequence number a polling host waits for (one rank, lio_icp_host.cpp pcl_wait)
+                                  // sequence number a polling host waits for (one rank: lio_icp_policy.hpp Mailbox)
 
 constexpr int kPclMaxKc = 1016;   // the largest GEMM depth block modelled (kc at a 48 KiB L1)
 constexpr int kPclTinyN = 16;     // n + 6 < 20: Eigen's lazy coefficient-based product (pcl_pack)
@@ -38,7 +38,7 @@ struct PclBuf {
     int64_t n_hint = 0;       // > 0: no more accepted pairs than this in the next passes (the source's points)
     SeqSumBuf means;          // 6 chains
     SeqSumBuf sig;            // 9 chains (order 1)
-    // sharded (world > 1, lio_icp_host.cpp): the whole chain's count (means.sh->n32), the first kPclTinyN pairs
+    // sharded (world > 1, lio_icp_stats.cpp): the whole chain's count (means.sh->n32), the first kPclTinyN pairs
     // of the whole source order (the lazy product), every rank's depth blocks in global order, and the ranks'
     // statuses combined: {means bad, means overflow, sigma bad, sigma overflow, look-back time-out}
     const uint32_t* n_all = nullptr;
@@ -53,7 +53,7 @@ struct PclBuf {
 int pcl_reserve_plain(PclBuf& p, int64_t n, hipStream_t st);
 int pcl_shard_reserve(PclBuf& p, int64_t n_blocks_global, hipStream_t st);
 
-// ---- sharded statistics (lio_icp_host.cpp fid_sharded): the means' seqsum event message carries this rank's
+// ---- sharded statistics (lio_icp_handle.hpp fid_sharded): the means' seqsum event message carries this rank's
 // first kPclMaxKc pairs (SeqHeads: a depth block starting in one window may end in the next; seq_shard_merge
 // appends the next ranks' after the window and puts the first kPclTinyN of the whole order in ghead)
 inline int64_t pcl_heads_words() { return 3 * (int64_t)kPclMaxKc; }

@@ -20,7 +20,7 @@
 // Chains are supplied by a source functor: value(c, k) of chain c at element k (k < n, n on the device).
 //
 // Sharded (SeqSumBuf::sh != nullptr): the chain's elements are split over ranks in order, this rank holding
-// the window [gbase, gbase + n) (lio_icp_host.cpp, the loop ICP over several GPUs).  Every rank predicts,
+// the window [gbase, gbase + n) (lio_icp_stats.cpp, the loop ICP over several GPUs).  Every rank predicts,
 // counts and lists the events of its own window — from the double prefix of the elements before it and a
 // binade floor common to all ranks (seq_bsum's block sums -> all-gather -> seq_shard_offsets) — the event lists
 // are all-gathered (seq_shard_pack -> all-gather -> seq_shard_merge: global positions and increment prefixes),

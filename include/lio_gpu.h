@@ -352,7 +352,7 @@ int lio_seqsum6(int device, const float* x, int64_t n, int flags, float* sums6, 
  * the capacity and differs between the calls of a pass, the same on every rank: the records (double
  * statistics, fitness passes); in the PCL float modes (the default) three all-gathers per pass — the
  * records followed by the window's chain totals, the window's float-chain event lists (and its first
- * pairs), the window's GEMM depth blocks (lio_icp_host.cpp, lio_seqsum.hpp); recv holds rank r at r * n. */
+ * pairs), the window's GEMM depth blocks (lio_icp_stats.cpp, lio_seqsum.hpp); recv holds rank r at r * n. */
 typedef int (*lio_allgather_dev_fn)(const double* d_send, int64_t n, double* d_recv, void* stream, void* user);
 int lio_icp_set_shard_device(lio_icp* h, int rank, int world, lio_allgather_dev_fn fn, void* user);
 int lio_icp_exchange_len(int64_t n_source, int world, int64_t* n_per_rank);

@@ -205,23 +205,39 @@ def test_icp_fidelity_recovery_paths(oracle):
         assert out[k][1] == out["normal"][1]
 
 
-def test_icp_lookback_timeout_does_not_poison_the_handle(oracle):
+_POISON_REF = {}  # order -> (src, dst, the oracle's transform), computed once
+
+
+def _poison_ref(oracle, order):
+    if order not in _POISON_REF:
+        src, dst, _ = synth.make_icp_pair(n_points=30_000, seed=12, disp=(1.0, 3.0))
+        _POISON_REF[order] = (src, dst, oracle.icp_align(src, dst, params=_float_params(oracle, order))["T"])
+    return _POISON_REF[order]
+
+
+@pytest.mark.parametrize("order", [2, 3])
+@pytest.mark.parametrize("hook", [(4, 0), (0, 8)], ids=["timeout", "listcap"])
+def test_icp_lookback_timeout_does_not_poison_the_handle(oracle, hook, order):
     """a compaction look-back time-out on one alignment (test hook) is cleared, so the next
-    alignment on the same handle takes the parallel path again with the same transform bits."""
-    src, dst, _ = synth.make_icp_pair(n_points=30_000, seed=12, disp=(1.0, 3.0))
-    lc = LC.LoopClosure(LC.LoopClosureConfig(), umeyama_float=2)
+    alignment on the same handle takes the parallel path again with the same transform bits.  ADVICE r06: so
+    does an alignment after one whose event lists overflowed (capped at 8).  Either way the first alignment
+    ends in the serial kernels, whose copy into the block the host polls must not be taken for the next pass's
+    statistics (orders 2 / 3 copy the pack's output: lio_icp_policy.hpp Mailbox)."""
+    src, dst, T_ref = _poison_ref(oracle, order)
+    lc = LC.LoopClosure(LC.LoopClosureConfig(), umeyama_float=order)
     lc.setInputSource(src)
     lc.setInputTarget(dst)
-    lc.set_fidelity_debug(4, 0)
+    lc.set_fidelity_debug(*hook)
     r0 = lc.align(keep_aligned=False)
     s0 = lc.fidelity_stats()
     lc.set_fidelity_debug(0, 0)
     r1 = lc.align(keep_aligned=False)
     s1 = lc.fidelity_stats()
-    assert s0["serial"] > 0 and s1["serial"] == s0["serial"]  # the second alignment never fell back
+    print(f"hook {hook} order {order}: {s0} -> {s1}")
+    assert s0["serial"] > 0  # the hook took the first alignment to the serial kernels
+    assert s1["serial"] == s0["serial"]  # the second alignment never fell back
     np.testing.assert_array_equal(np.array(list(r0.T), np.float32), np.array(list(r1.T), np.float32))
-    o = oracle.icp_align(src, dst, params=_float_params(oracle, 2))
-    np.testing.assert_allclose(np.array(list(r1.T), np.float32).reshape(4, 4), o["T"], atol=1e-5)
+    np.testing.assert_allclose(np.array(list(r1.T), np.float32).reshape(4, 4), T_ref, atol=1e-5)
 
 
 @pytest.mark.parametrize("disp", [(0.3, 1.5), (2.5, 4.0)])
@@ -332,3 +348,48 @@ def test_icp_device_exchange_emulated_ranks(world, mode, debug):
         print(debug[0], fs)
         key = "repasses" if debug[0] == "repass" else "serial"
         assert all(f[key] > 0 for f in fs) and len({f[key] for f in fs}) == 1  # every rank took the same path
+
+
+@pytest.mark.parametrize("mode", [LC.DOUBLE_STATS, LC.FIDELITY_ORDER], ids=["records", "sharded-float"])
+def test_icp_failing_host_allgather_is_reported(mode):
+    """A host all-gather callback that returns non-zero and leaves no message of its own: the alignment fails
+    with "allgather callback failed" (the text callers match; a callee's own message would follow it), through
+    both host forms of the exchange: the records alone (double statistics) and the staged device buffers (the
+    sharded float orders).  Two ranks as threads, both callbacks failing in their first call, so no rank waits
+    for a peer."""
+    import threading
+
+    from lio_gpu import _capi
+
+    src, dst, _ = synth.make_icp_pair(n_points=8_000, seed=3)
+    world = 2
+    calls = [0] * world
+    errors = [None] * world
+
+    def make_cb(rank):
+        def cb(send_p, n, recv_p, user):
+            calls[rank] += 1
+            return -1
+
+        return _capi.ALLGATHER_FN(cb)
+
+    cbs = [make_cb(r) for r in range(world)]
+    lcs = [LC.LoopClosure(LC.LoopClosureConfig(), umeyama_float=mode) for _ in range(world)]
+
+    def run(rank):
+        lcs[rank].set_shard(rank, world, cbs[rank])
+        lcs[rank].setInputSource(src)
+        lcs[rank].setInputTarget(dst)
+        try:
+            lcs[rank].align(keep_aligned=False)
+        except _capi.LioError as e:
+            errors[rank] = e
+
+    th = [threading.Thread(target=run, args=(r,)) for r in range(world)]
+    [t.start() for t in th]
+    [t.join(timeout=120) for t in th]
+    for r in range(world):
+        assert calls[r] == 1 and errors[r] is not None, (r, calls[r], errors[r])
+        assert errors[r].code == _capi.LIO_ERR_STATE
+        assert "allgather callback failed" in str(errors[r])
+        assert str(errors[r]).endswith("allgather callback failed")  # nothing appended: the callee said nothing
