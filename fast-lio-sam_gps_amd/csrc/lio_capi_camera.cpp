@@ -1,9 +1,10 @@
 // lio_capi_camera.cpp — the C-ABI (include/lio_gpu.h) of the camera leg: lio_project_points and
-// lio_undistort_map on a lio_filter, the lio_colorizer and the lio_undistorter.
+// lio_undistort_map on a lio_filter, the lio_colorizer, the lio_undistorter and the lio_exposure.
 #include <limits>
 
 #include "lio_capi_util.hpp"
 #include "lio_colorize.hpp"
+#include "lio_exposure.hpp"
 #include "lio_undistort.hpp"
 
 using namespace lio::capi;
@@ -248,6 +249,125 @@ int lio_undistorter_get_timing(lio_undistorter* h, double* ms3) {
     if (rc) return rc;
     if (!ms3) return fail(LIO_ERR_ARG, "lio_undistorter_get_timing: ms3 is NULL");
     for (int k = 0; k < lio::kUdStages; ++k) ms3[k] = h->u.ms[k];
+    return LIO_OK;
+}
+
+// ---- exposure adaption (lio_exposure.hip) ----
+// The checks of an image and its result that need no device; they come before the handle is looked at.  out may
+// be absent (lio_exposure_histograms).
+static int exposure_image_arg(const std::string& what, const void* image, int width, int height, int channels, int64_t pitch,
+                              int order, const void* out, bool has_out, int64_t out_pitch) {
+    if (!image) return fail(LIO_ERR_ARG, what + ": image is NULL");
+    if (has_out && !out) return fail(LIO_ERR_ARG, what + ": out is NULL");
+    if (width < 1 || width > lio::kExMaxSize || height < 1 || height > lio::kExMaxSize)
+        return fail(LIO_ERR_ARG, what + ": width and height must be in 1..32767");
+    if (channels != 1 && channels != 3) return fail(LIO_ERR_ARG, what + ": channels must be 1 or 3");
+    if (order != 0 && order != 1) return fail(LIO_ERR_ARG, what + ": order must be 0 (B G R) or 1 (R G B)");
+    if (pitch < (int64_t)channels * width) return fail(LIO_ERR_ARG, what + ": pitch must be at least channels x width bytes");
+    if (has_out && out_pitch < (int64_t)channels * width)
+        return fail(LIO_ERR_ARG, what + ": out_pitch must be at least channels x width bytes");
+    return LIO_OK;
+}
+
+static int exposure_tiles_arg(const std::string& what, int tiles_x, int tiles_y) {
+    if (tiles_x < 1 || tiles_x > lio::kExMaxTiles || tiles_y < 1 || tiles_y > lio::kExMaxTiles)
+        return fail(LIO_ERR_ARG, what + ": tiles_x and tiles_y must be in 1..64");
+    return LIO_OK;
+}
+
+static int exposure_tiling_arg(const std::string& what, int width, int height, double clip_limit, int tiles_x, int tiles_y,
+                               lio::ExTiling* t) {
+    const char* why = "";
+    if (lio::exposure_tiling(width, height, clip_limit, tiles_x, tiles_y, t, &why)) return fail(LIO_ERR_ARG, what + ": " + why);
+    return LIO_OK;
+}
+
+struct lio_exposure : Handle {
+    lio::ExposureBuf e;
+};
+
+int lio_exposure_destroy(lio_exposure* h) {
+    return close_handle(h, [](lio_exposure& z) { lio::exposure_free(z.e); });
+}
+
+int lio_exposure_create(int device, lio_exposure** out) {
+    int rc = open_handle(device, out, "lio_exposure_create: out is NULL");
+    if (rc) return rc;
+    if ((rc = status(lio::exposure_init((*out)->e), "lio_exposure_create"))) {
+        lio_exposure_destroy(*out);
+        *out = nullptr;
+    }
+    return rc;
+}
+
+int lio_exposure_histograms(lio_exposure* h, const uint8_t* image, int width, int height, int channels, int64_t pitch,
+                            int order, int64_t* hist_v_opt, int64_t* hist_gray_opt) {
+    const char* what = "lio_exposure_histograms";
+    int rc = exposure_image_arg(what, image, width, height, channels, pitch, order, nullptr, false, 0);
+    if (rc) return rc;
+    if ((rc = null_handle(h, what))) return rc;
+    HIP_TRY(hipSetDevice(h->dev));
+    return status(lio::exposure_histograms(h->e, image, width, height, channels, pitch, order, hist_v_opt, hist_gray_opt, h->st),
+                  what);
+}
+
+int lio_exposure_clahe(lio_exposure* h, const uint8_t* image, int width, int height, int channels, int64_t pitch, int order,
+                       double clip_limit, int tiles_x, int tiles_y, uint8_t* out, int64_t out_pitch) {
+    const char* what = "lio_exposure_clahe";
+    int rc = exposure_image_arg(what, image, width, height, channels, pitch, order, out, true, out_pitch);
+    if (rc) return rc;
+    if ((rc = exposure_tiles_arg(what, tiles_x, tiles_y))) return rc;
+    lio::ExTiling t{};
+    if ((rc = exposure_tiling_arg(what, width, height, clip_limit, tiles_x, tiles_y, &t))) return rc;
+    if ((rc = null_handle(h, what))) return rc;
+    HIP_TRY(hipSetDevice(h->dev));
+    return status(lio::exposure_clahe(h->e, image, width, height, channels, pitch, order, t, out, out_pitch, h->st), what);
+}
+
+int lio_exposure_remap(lio_exposure* h, const uint8_t* image, int width, int height, int channels, int64_t pitch, int order,
+                       const uint8_t* lut_v_opt, const uint8_t* lut_all_opt, uint8_t* out, int64_t out_pitch) {
+    const char* what = "lio_exposure_remap";
+    int rc = exposure_image_arg(what, image, width, height, channels, pitch, order, out, true, out_pitch);
+    if (rc) return rc;
+    if (!lut_v_opt && !lut_all_opt) return fail(LIO_ERR_ARG, std::string(what) + ": lut_v_opt and lut_all_opt are both NULL");
+    if ((rc = null_handle(h, what))) return rc;
+    HIP_TRY(hipSetDevice(h->dev));
+    return status(lio::exposure_remap(h->e, image, width, height, channels, pitch, order, lut_v_opt, lut_all_opt, out, out_pitch,
+                                      h->st),
+                  what);
+}
+
+int lio_exposure_clahe_undistorted(lio_exposure* h, lio_undistorter* undistorter, const uint8_t* raw_image, int64_t pitch,
+                                   int order, double clip_limit, int tiles_x, int tiles_y, uint8_t* out, int64_t out_pitch) {
+    const std::string what = "lio_exposure_clahe_undistorted";
+    if (!raw_image) return fail(LIO_ERR_ARG, what + ": raw_image is NULL");
+    if (!out) return fail(LIO_ERR_ARG, what + ": out is NULL");
+    if (order != 0 && order != 1) return fail(LIO_ERR_ARG, what + ": order must be 0 (B G R) or 1 (R G B)");
+    int rc = exposure_tiles_arg(what, tiles_x, tiles_y);
+    if (rc) return rc;
+    if (!(clip_limit == clip_limit)) return fail(LIO_ERR_ARG, what + ": clip_limit x tile area / 256 must be below 2^31 and not NaN");
+    if ((rc = null_handle(h, what.c_str()))) return rc;
+    if (!undistorter) return fail(LIO_ERR_ARG, what + ": undistorter is NULL");
+    if (undistorter->dev != h->dev) return fail(LIO_ERR_ARG, what + ": both handles must be on one device");
+    const lio::UndistortBuf& u = undistorter->u;
+    if (!u.have_camera) return fail(LIO_ERR_STATE, what + ": no camera (call lio_undistorter_set_camera first)");
+    if (pitch < (int64_t)u.channels * u.sw)
+        return fail(LIO_ERR_ARG, what + ": pitch must be at least channels x width bytes of the raw image");
+    if (out_pitch < (int64_t)u.channels * u.dw)
+        return fail(LIO_ERR_ARG, what + ": out_pitch must be at least channels x width bytes of the rectified image");
+    lio::ExTiling t{};
+    if ((rc = exposure_tiling_arg(what, u.dw, u.dh, clip_limit, tiles_x, tiles_y, &t))) return rc;
+    HIP_TRY(hipSetDevice(h->dev));
+    // the undistorter's own stream is idle between its calls (each waits for it): its buffers are used on h's stream
+    return status(lio::exposure_clahe_undistorted(h->e, undistorter->u, raw_image, pitch, order, t, out, out_pitch, h->st),
+                  what.c_str());
+}
+
+int lio_exposure_get_timing(lio_exposure* h, double* ms5) {
+    if (!ms5) return fail(LIO_ERR_ARG, "lio_exposure_get_timing: ms5 is NULL");
+    const int rc = null_handle(h, "lio_exposure_get_timing");
+    if (rc) return rc;
+    for (int k = 0; k < lio::kExStages; ++k) ms5[k] = h->e.ms[k];
     return LIO_OK;
 }
 

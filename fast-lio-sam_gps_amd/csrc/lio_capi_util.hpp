@@ -45,7 +45,7 @@ static inline bool all_finite(const double* v, int64_t count) {
     return true;
 }
 
-// ---- the handle shell: lio_filter, lio_colorizer and lio_undistorter are a Handle and their buffers ----
+// ---- the handle shell: lio_filter, lio_colorizer, lio_undistorter and lio_exposure are a Handle and their buffers ----
 struct Handle {
     int dev = 0;
     hipStream_t st = nullptr;

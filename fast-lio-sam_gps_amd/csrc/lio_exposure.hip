@@ -1,0 +1,488 @@
+// lio_exposure.hip — exposure adaption on gfx950: the per-frame work of the reference's
+// post_process/exposure_adaption scripts (lio_exposure.hpp), restated as our own contract (include/lio_gpu.h:
+// lio_exposure_*): OpenCV's 8-bit BGR -> HSV in integers, CLAHE of one plane, HSV -> BGR in float32, table remaps.
+// The file is compiled with -ffp-contract=off, host and device: no multiply-add is fused anywhere.
+//
+//   ex_hist_kernel   several workgroups per tile, each over a stripe of the tile's rows of the EXTENDED plane (the
+//                    reflected border counts); a thread takes 4 consecutive pixels, loaded as ud_remap_kernel loads
+//                    its taps, and adds V (or gray) into one of 16 copies of the 256 bins in LDS (copy = thread &
+//                    15, copies 257 words apart): a saturated sky, every pixel in bin 255, meets 16 addresses on 16
+//                    banks per wave instead of one.  The copies are summed and flushed with one global atomicAdd
+//                    per non-empty bin into uint32 hist[tile][256], cleared by a memset on the stream.  Integer
+//                    counts: the result does not depend on the order.
+//   ex_lut_kernel    one 256-thread workgroup per tile, thread i owns bin i: the excess by a block reduction, the
+//                    closed-form residual, an inclusive scan, the table byte.
+//   ex_apply_kernel  4 pixels of a row per thread (block 64 x 4: a wave is 256 consecutive pixels of one row): the
+//                    conversions, four table gathers per pixel and the float32 interpolation; 4 * channels bytes
+//                    out as dwords into device rows that are a multiple of 4 bytes, the last partial group as bytes.
+//                    The tables (16 KB at 8 x 8 tiles) are left to the cache: staging the few tables a block can
+//                    reach in LDS gave the same bits and the same time (profiles/exposure_ab.md).  The same kernel
+//                    with MODE 1 is the table remap of lio_exposure_remap.
+#include <cstring>
+
+#include "lio_camera.hpp"
+#include "lio_exposure.hpp"
+#include "lio_scratch.hpp"
+
+namespace lio {
+namespace {
+
+// ---- the division tables of the 8-bit BGR -> HSV: sdiv[i] = rint((255 << 12) / i), hdiv[i] = rint((180 << 12) / (6 i)).
+// The quotients are below 2^21 and an exact tie is a tie in double too, so the integer rounding below (ties to
+// even) is the double rint of the contract.
+struct ExDivTab {
+    int32_t v[256];
+};
+constexpr int32_t ex_rdiv(int64_t a, int64_t b) {
+    int64_t q = a / b;
+    const int64_t r = a % b;
+    if (2 * r > b || (2 * r == b && (q & 1))) ++q;
+    return (int32_t)q;
+}
+constexpr ExDivTab ex_make_div(int64_t num, int64_t per) {
+    ExDivTab t{};
+    for (int i = 1; i < 256; ++i) t.v[i] = ex_rdiv(num, per * i);
+    return t;
+}
+static_assert(ex_rdiv(255 << 12, 255) == 4096 && ex_rdiv(180 << 12, 6) == 122880 && ex_rdiv(5, 2) == 2 && ex_rdiv(7, 2) == 4,
+              "rint of a quotient, ties to even");
+__constant__ const ExDivTab ex_sdiv = ex_make_div(255 << 12, 1);
+__constant__ const ExDivTab ex_hdiv = ex_make_div(180 << 12, 6);
+
+constexpr float kExHs = 0x1.111112p-5f;  // the float nearest 1/30
+constexpr float kExK = 0x1.010102p-8f;   // the float nearest 1/255
+
+__device__ __forceinline__ int ex_sat_rint(float x) { return min(max((int)rintf(x), 0), 255); }
+
+__device__ __forceinline__ void ex_bgr2hsv(int b, int g, int r, int& h, int& s, int& v) {
+    v = max(b, max(g, r));
+    const int vmin = min(b, min(g, r));
+    const int d = v - vmin;
+    s = (d * ex_sdiv.v[v] + 2048) >> 12;
+    const int h0 = v == r ? g - b : (v == g ? b - r + 2 * d : r - g + 4 * d);
+    h = (h0 * ex_hdiv.v[d] + 2048) >> 12;
+    if (h < 0) h += 180;
+}
+
+__device__ __forceinline__ void ex_hsv2bgr(int h, int s, int v, int& b, int& g, int& r) {
+    const float vf = (float)v * kExK;
+    if (s == 0) {
+        b = g = r = ex_sat_rint(vf * 255.0f);
+        return;
+    }
+    const float hf = (float)h * kExHs, sf = (float)s * kExK;
+    int sec = (int)floorf(hf);
+    float f = hf - (float)sec;
+    if (sec >= 6) sec = 0, f = 0.f;
+    const float t0 = vf, t1 = vf * (1.f - sf), t2 = vf * (1.f - sf * f), t3 = vf * (1.f - sf * (1.f - f));
+    float fb, fg, fr;  // the sector table {1,3,0},{1,0,2},{3,0,1},{0,2,1},{0,1,3},{2,1,0}
+    switch (sec) {
+        case 0: fb = t1, fg = t3, fr = t0; break;
+        case 1: fb = t1, fg = t0, fr = t2; break;
+        case 2: fb = t3, fg = t0, fr = t1; break;
+        case 3: fb = t0, fg = t2, fr = t1; break;
+        case 4: fb = t0, fg = t1, fr = t3; break;
+        default: fb = t2, fg = t1, fr = t0; break;
+    }
+    b = ex_sat_rint(fb * 255.0f), g = ex_sat_rint(fg * 255.0f), r = ex_sat_rint(fr * 255.0f);
+}
+
+__device__ __forceinline__ int ex_gray(int b, int g, int r) { return (3735 * b + 19235 * g + 9798 * r + 16384) >> 15; }
+
+// the 4 * C bytes of 4 consecutive pixels at p, at any alignment, one value per byte
+template <int C>
+__device__ __forceinline__ void ex_load4(const uint8_t* __restrict__ p, uint32_t* v) {
+    uint32_t w[C];
+    __builtin_memcpy(w, p, 4 * C);
+#pragma unroll
+    for (int k = 0; k < 4 * C; ++k) v[k] = (w[k >> 2] >> (8 * (k & 3))) & 0xffu;
+}
+
+// V (gray != 0: gray) of the pixel whose C bytes are c
+template <int C>
+__device__ __forceinline__ int ex_value(const uint32_t* c, int order, int gray) {
+    if constexpr (C == 1) {
+        return (int)c[0];
+    } else {
+        const int b = (int)(order ? c[2] : c[0]), g = (int)c[1], r = (int)(order ? c[0] : c[2]);
+        return gray ? ex_gray(b, g, r) : max(b, max(g, r));
+    }
+}
+
+constexpr int kExCopies = 16, kExCopyStride = 257;
+
+// grid (tiles, stripes): the rows [blockIdx.y * rows_per, + rows_per) of tile blockIdx.x of the extended plane.
+// x >= W reads 2 (W - 1) - x, rows likewise (the host has checked that the padding is at most the size - 1).
+template <int C>
+__global__ __launch_bounds__(256) void ex_hist_kernel(const uint8_t* __restrict__ img, int64_t pitch, int W, int H, int order,
+                                                      int gray, int tiles_x, int tw, int th, int rows_per,
+                                                      uint32_t* __restrict__ hist) {
+    __shared__ uint32_t bins[kExCopies * kExCopyStride];
+    const int tid = (int)threadIdx.x;
+    for (int i = tid; i < kExCopies * kExCopyStride; i += 256) bins[i] = 0;
+    __syncthreads();
+    const int tile = (int)blockIdx.x, ty = tile / tiles_x, tx = tile % tiles_x;
+    const int r0 = (int)blockIdx.y * rows_per, r1 = min(th, r0 + rows_per);
+    const int gpr = (tw + 3) >> 2;  // groups of 4 pixels per tile row
+    const int items = max(r1 - r0, 0) * gpr;
+    uint32_t* mine = bins + (tid & (kExCopies - 1)) * kExCopyStride;
+    for (int it = tid; it < items; it += 256) {
+        const int c0 = 4 * (it % gpr), n = min(4, tw - c0);
+        const int ey = ty * th + r0 + it / gpr, ex = tx * tw + c0;
+        const int sy = ey < H ? ey : max(2 * (H - 1) - ey, 0);
+        const uint8_t* row = img + (int64_t)sy * pitch;
+        if (n == 4 && ex + 3 < W) {
+            uint32_t v[4 * C];
+            ex_load4<C>(row + (int64_t)ex * C, v);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) atomicAdd(&mine[ex_value<C>(v + k * C, order, gray)], 1u);
+        } else {
+            for (int k = 0; k < n; ++k) {
+                const int x = ex + k, sx = x < W ? x : max(2 * (W - 1) - x, 0);
+                uint32_t v[C];
+#pragma unroll
+                for (int c = 0; c < C; ++c) v[c] = row[(int64_t)sx * C + c];
+                atomicAdd(&mine[ex_value<C>(v, order, gray)], 1u);
+            }
+        }
+    }
+    __syncthreads();
+    uint32_t sum = 0;
+#pragma unroll
+    for (int k = 0; k < kExCopies; ++k) sum += bins[k * kExCopyStride + tid];
+    if (sum) atomicAdd(&hist[(int64_t)tile * 256 + tid], sum);
+}
+
+// grid (tiles): hist[tile] -> lut[tile].  clip 0: no clipping.  scale = 255.0f / (float)area.
+__global__ __launch_bounds__(256) void ex_lut_kernel(const uint32_t* __restrict__ hist, int clip, float scale,
+                                                     uint8_t* __restrict__ lut) {
+    __shared__ int sh[256];
+    const int i = (int)threadIdx.x;
+    const int64_t at = (int64_t)blockIdx.x * 256 + i;
+    int h = (int)hist[at];
+    if (clip > 0) {
+        sh[i] = max(h - clip, 0);
+        __syncthreads();
+        for (int s = 128; s > 0; s >>= 1) {
+            if (i < s) sh[i] += sh[i + s];
+            __syncthreads();
+        }
+        const int excess = sh[0];
+        __syncthreads();
+        h = min(h, clip);
+        const int batch = excess / 256, res = excess - 256 * batch;
+        h += batch;
+        if (res > 0) {
+            const int step = max(256 / res, 1);
+            if (i % step == 0 && i / step < res) ++h;
+        }
+    }
+    sh[i] = h;
+    __syncthreads();
+    for (int off = 1; off < 256; off <<= 1) {  // inclusive scan
+        const int add = i >= off ? sh[i - off] : 0;
+        __syncthreads();
+        sh[i] += add;
+        __syncthreads();
+    }
+    lut[at] = (uint8_t)ex_sat_rint((float)sh[i] * scale);
+}
+
+struct ExApplyArg {
+    int W, H, order;
+    int tiles_x, tiles_y;
+    float inv_tw, inv_th;  // 1.0f / (float)tw, 1.0f / (float)th
+    int has_v, has_all;    // MODE 1: lut holds lut_v (256) then lut_all (256)
+};
+
+// the tile pair and the weights of one coordinate: (float)x * inv - 0.5f, its floor and fraction
+struct ExAxis {
+    int t1, t2;
+    float a, a1;
+};
+__device__ __forceinline__ ExAxis ex_axis(int x, float inv, int tiles) {
+    const float f = (float)x * inv - 0.5f;
+    const int t = (int)floorf(f);
+    ExAxis o;
+    o.a = f - (float)t;
+    o.a1 = 1.f - o.a;
+    o.t2 = min(t + 1, tiles - 1);
+    o.t1 = min(max(t, 0), tiles - 1);  // t <= tiles - 1 for every x of the plane; the upper bound only guards memory
+    return o;
+}
+
+// MODE 0: CLAHE; 1: table remap.  img rows of `pitch` bytes at any alignment; out rows out_pitch bytes, a multiple of
+// 4 and this file's own buffer.
+template <int C, int MODE>
+__global__ __launch_bounds__(256) void ex_apply_kernel(const uint8_t* __restrict__ img, int64_t pitch, ExApplyArg a,
+                                                       const uint8_t* __restrict__ lut, uint8_t* __restrict__ out,
+                                                       int64_t out_pitch) {
+    const int x = 4 * ((int)blockIdx.x * 64 + (int)threadIdx.x);
+    const int row = (int)blockIdx.y * 4 + (int)threadIdx.y;
+    if (row >= a.H || x >= a.W) return;
+    const int n = min(4, a.W - x);
+    const uint8_t* src = img + (int64_t)row * pitch + (int64_t)x * C;
+    uint32_t v[4 * C];
+    if (n == 4) {
+        ex_load4<C>(src, v);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 3 * C; ++k) v[k] = k < n * C ? src[k] : 0u;
+#pragma unroll
+        for (int k = 3 * C; k < 4 * C; ++k) v[k] = 0u;
+    }
+    ExAxis ay{};
+    if constexpr (MODE == 0) ay = ex_axis(row, a.inv_th, a.tiles_y);
+    auto table = [&](int ty, int tx, int p) -> float { return (float)lut[((int64_t)ty * a.tiles_x + tx) * 256 + p]; };
+    // the new value of plane value p at column xx
+    auto adapt = [&](int p, int xx) -> int {
+        if constexpr (MODE == 1) {
+            return a.has_v ? (int)lut[p] : p;
+        } else {
+            const ExAxis ax = ex_axis(xx, a.inv_tw, a.tiles_x);
+            const float top = table(ay.t1, ax.t1, p) * ax.a1 + table(ay.t1, ax.t2, p) * ax.a;
+            const float bot = table(ay.t2, ax.t1, p) * ax.a1 + table(ay.t2, ax.t2, p) * ax.a;
+            return ex_sat_rint(top * ay.a1 + bot * ay.a);
+        }
+    };
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        if (k >= n) break;
+        uint32_t* c = v + k * C;
+        if constexpr (C == 1) {
+            int p = adapt((int)c[0], x + k);
+            if (MODE == 1 && a.has_all) p = lut[256 + p];
+            c[0] = (uint32_t)p;
+        } else {
+            int b = (int)(a.order ? c[2] : c[0]), g = (int)c[1], r = (int)(a.order ? c[0] : c[2]);
+            if (MODE == 0 || a.has_v) {
+                int h, s, val;
+                ex_bgr2hsv(b, g, r, h, s, val);
+                ex_hsv2bgr(h, s, adapt(val, x + k), b, g, r);
+            }
+            if (MODE == 1 && a.has_all) b = lut[256 + b], g = lut[256 + g], r = lut[256 + r];
+            c[0] = (uint32_t)(a.order ? r : b), c[1] = (uint32_t)g, c[2] = (uint32_t)(a.order ? b : r);
+        }
+    }
+    uint8_t* o = out + (int64_t)row * out_pitch + (int64_t)x * C;
+    if (n == 4) {
+        uint32_t* o4 = reinterpret_cast<uint32_t*>(o);
+#pragma unroll
+        for (int k = 0; k < C; ++k) o4[k] = v[4 * k] | (v[4 * k + 1] << 8) | (v[4 * k + 2] << 16) | (v[4 * k + 3] << 24);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 3 * C; ++k)
+            if (k < n * C) o[k] = (uint8_t)v[k];
+    }
+}
+
+// the device row pitch of a result: channels * width rounded up to 4 bytes
+int64_t ex_pitch(int width, int channels) { return (int64_t)(((size_t)width * (size_t)channels + 3) & ~(size_t)3); }
+
+size_t ex_in_bytes(int width, int height, int channels, int64_t pitch) {
+    // the last row ends after its channels * width bytes: nothing past it is read from the caller's buffer
+    return (size_t)(height - 1) * (size_t)pitch + (size_t)width * (size_t)channels;
+}
+
+// everything a run of `tiles` tiles needs besides the input, reserved before anything is enqueued: the arena
+// (hist, lut), the result and its staging
+int ex_reserve(ExposureBuf& e, int64_t tiles, int width, int height, int channels, uint32_t** hist, uint8_t** lut) {
+    auto fields = [&](Carver& c) {
+        c(*hist, (size_t)tiles * 256);
+        c(*lut, (size_t)std::max<int64_t>(tiles, 2) * 256);
+    };
+    int rc = reserve_arena(&e.arena, e.arena_bytes, fields);
+    const size_t out_bytes = (size_t)ex_pitch(width, channels) * (size_t)height;
+    if (!rc && out_bytes) rc = grow_pinned(&e.h_out, e.h_out_bytes, out_bytes, kImageStageFloor);
+    if (!rc && out_bytes) rc = grow_scratch(reinterpret_cast<void**>(&e.out), e.out_bytes, out_bytes);
+    return rc;
+}
+
+// ev[0] .. ev[1]: the frame into e.img
+int ex_upload(ExposureBuf& e, const uint8_t* image, size_t in_bytes, hipStream_t st) {
+    int rc = grow_pinned(&e.h_img, e.h_img_bytes, in_bytes, kImageStageFloor);
+    if (!rc) rc = grow_scratch(reinterpret_cast<void**>(&e.img), e.img_bytes, in_bytes);
+    if (rc) return rc;
+    LIO_HIP(hipEventRecord(e.ev[kExUpload], st));
+    std::memcpy(e.h_img, image, in_bytes);
+    LIO_HIP(hipMemcpyAsync(e.img, e.h_img, in_bytes, hipMemcpyHostToDevice, st));
+    LIO_HIP(hipEventRecord(e.ev[kExHist], st));
+    return kOk;
+}
+
+// hist[tiles][256] of V (gray: of gray) of the device image, cleared first
+int ex_launch_hist(const uint8_t* d_img, int64_t pitch, int width, int height, int channels, int order, int gray, int tiles_x,
+                   int tiles_y, int tw, int th, uint32_t* hist, hipStream_t st) {
+    const int tiles = tiles_x * tiles_y;
+    LIO_HIP(hipMemsetAsync(hist, 0, (size_t)tiles * 256 * sizeof(uint32_t), st));
+    const int rows_per = std::min(th, std::max(1, (8192 + tw - 1) / tw));  // about 8192 pixels per workgroup
+    const dim3 grid((unsigned)tiles, (unsigned)((th + rows_per - 1) / rows_per));
+    if (channels == 3)
+        ex_hist_kernel<3><<<grid, 256, 0, st>>>(d_img, pitch, width, height, order, gray, tiles_x, tw, th, rows_per, hist);
+    else
+        ex_hist_kernel<1><<<grid, 256, 0, st>>>(d_img, pitch, width, height, order, gray, tiles_x, tw, th, rows_per, hist);
+    LIO_HIP(hipGetLastError());
+    return kOk;
+}
+
+template <int MODE>
+int ex_launch_apply(const uint8_t* d_img, int64_t pitch, int channels, const ExApplyArg& a, const uint8_t* lut, uint8_t* out,
+                    hipStream_t st) {
+    const dim3 block(64, 4), grid((unsigned)((a.W + 255) / 256), (unsigned)((a.H + 3) / 4));
+    const int64_t out_pitch = ex_pitch(a.W, channels);
+    if (channels == 3)
+        ex_apply_kernel<3, MODE><<<grid, block, 0, st>>>(d_img, pitch, a, lut, out, out_pitch);
+    else
+        ex_apply_kernel<1, MODE><<<grid, block, 0, st>>>(d_img, pitch, a, lut, out, out_pitch);
+    LIO_HIP(hipGetLastError());
+    return kOk;
+}
+
+// ev[1] .. ev[4]: histograms, tables and the apply of the device image into e.out
+int ex_clahe_device(ExposureBuf& e, const uint8_t* d_img, int64_t pitch, int width, int height, int channels, int order,
+                    const ExTiling& t, uint32_t* hist, uint8_t* lut, hipStream_t st) {
+    int rc = ex_launch_hist(d_img, pitch, width, height, channels, order, 0, t.tiles_x, t.tiles_y, t.tw, t.th, hist, st);
+    if (rc) return rc;
+    LIO_HIP(hipEventRecord(e.ev[kExLut], st));
+    const float scale = 255.0f / (float)(t.tw * t.th);
+    ex_lut_kernel<<<t.tiles_x * t.tiles_y, 256, 0, st>>>(hist, t.clip, scale, lut);
+    LIO_HIP(hipGetLastError());
+    LIO_HIP(hipEventRecord(e.ev[kExApply], st));
+    ExApplyArg a{};
+    a.W = width, a.H = height, a.order = order, a.tiles_x = t.tiles_x, a.tiles_y = t.tiles_y;
+    a.inv_tw = 1.0f / (float)t.tw, a.inv_th = 1.0f / (float)t.th;
+    if ((rc = ex_launch_apply<0>(d_img, pitch, channels, a, lut, e.out, st))) return rc;
+    LIO_HIP(hipEventRecord(e.ev[kExDownload], st));
+    return kOk;
+}
+
+// ev[4] .. ev[5]: e.out to the caller's rows, channels * width bytes each (its padding is not touched); the wait
+// and the stage times
+int ex_download(ExposureBuf& e, int width, int height, int channels, uint8_t* out, int64_t out_pitch, hipStream_t st) {
+    const size_t row_bytes = (size_t)width * (size_t)channels;
+    const int64_t d_pitch = ex_pitch(width, channels);
+    const size_t out_bytes = (size_t)d_pitch * (size_t)height;
+    LIO_HIP(hipMemcpyAsync(e.h_out, e.out, out_bytes, hipMemcpyDeviceToHost, st));
+    LIO_HIP(hipEventRecord(e.ev[kExStages], st));
+    LIO_HIP(hipStreamSynchronize(st));
+    for (int k = 0; k < kExStages; ++k) LIO_HIP(hipEventElapsedTime(&e.ms[k], e.ev[k], e.ev[k + 1]));
+    if (out_pitch == d_pitch && row_bytes == (size_t)d_pitch)
+        std::memcpy(out, e.h_out, out_bytes);
+    else
+        for (int i = 0; i < height; ++i)
+            std::memcpy(out + (size_t)i * (size_t)out_pitch, e.h_out + (size_t)i * (size_t)d_pitch, row_bytes);
+    return kOk;
+}
+
+}  // namespace
+
+int exposure_tiling(int width, int height, double clip_limit, int tiles_x, int tiles_y, ExTiling* t, const char** why) {
+    t->tiles_x = tiles_x, t->tiles_y = tiles_y;
+    t->ext_w = width, t->ext_h = height;
+    if (width % tiles_x != 0 || height % tiles_y != 0) {
+        const int pad_w = tiles_x - width % tiles_x, pad_h = tiles_y - height % tiles_y;
+        if (pad_w > width - 1 || pad_h > height - 1) {
+            *why = "the reflected padding (tiles_x - width % tiles_x columns, tiles_y - height % tiles_y rows) must be at most "
+                   "width - 1 and height - 1";
+            return kArg;
+        }
+        t->ext_w = width + pad_w, t->ext_h = height + pad_h;
+    }
+    t->tw = t->ext_w / tiles_x, t->th = t->ext_h / tiles_y;
+    t->clip = 0;
+    if (!(clip_limit <= 0.0)) {
+        const double c = clip_limit * (double)(t->tw * t->th) / 256.0;
+        if (!(c < 2147483648.0)) {
+            *why = "clip_limit x tile area / 256 must be below 2^31 and not NaN";
+            return kArg;
+        }
+        t->clip = std::max((int)c, 1);
+    }
+    return kOk;
+}
+
+int exposure_init(ExposureBuf& e) {
+    for (hipEvent_t& ev : e.ev) LIO_HIP(hipEventCreate(&ev));
+    return grow_pinned(&e.h_small, e.h_small_bytes, 2 * 256 * sizeof(uint32_t), 0);
+}
+
+void exposure_free(ExposureBuf& e) {
+    dev_free(&e.img, &e.out, &e.arena);
+    host_free(&e.h_img, &e.h_out, &e.h_small);
+    for (hipEvent_t ev : e.ev)
+        if (ev) (void)hipEventDestroy(ev);
+    e = ExposureBuf{};
+}
+
+int exposure_histograms(ExposureBuf& e, const uint8_t* image, int width, int height, int channels, int64_t pitch, int order,
+                        int64_t* hist_v_opt, int64_t* hist_gray_opt, hipStream_t st) {
+    uint32_t* hist = nullptr;
+    uint8_t* lut = nullptr;
+    int rc = ex_reserve(e, 2, 0, 0, channels, &hist, &lut);  // two 1 x 1 tilings: V, then gray
+    if (rc) return rc;
+    if ((rc = ex_upload(e, image, ex_in_bytes(width, height, channels, pitch), st))) return rc;
+    if (hist_v_opt && (rc = ex_launch_hist(e.img, pitch, width, height, channels, order, 0, 1, 1, width, height, hist, st)))
+        return rc;
+    if (hist_gray_opt &&
+        (rc = ex_launch_hist(e.img, pitch, width, height, channels, order, 1, 1, 1, width, height, hist + 256, st)))
+        return rc;
+    for (int k = kExLut; k <= kExDownload; ++k) LIO_HIP(hipEventRecord(e.ev[k], st));
+    LIO_HIP(hipMemcpyAsync(e.h_small, hist, 2 * 256 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    LIO_HIP(hipEventRecord(e.ev[kExStages], st));
+    LIO_HIP(hipStreamSynchronize(st));
+    for (int k = 0; k < kExStages; ++k) LIO_HIP(hipEventElapsedTime(&e.ms[k], e.ev[k], e.ev[k + 1]));
+    for (int i = 0; i < 256; ++i) {
+        if (hist_v_opt) hist_v_opt[i] = (int64_t)e.h_small[i];
+        if (hist_gray_opt) hist_gray_opt[i] = (int64_t)e.h_small[256 + i];
+    }
+    return kOk;
+}
+
+int exposure_clahe(ExposureBuf& e, const uint8_t* image, int width, int height, int channels, int64_t pitch, int order,
+                   const ExTiling& t, uint8_t* out, int64_t out_pitch, hipStream_t st) {
+    uint32_t* hist = nullptr;
+    uint8_t* lut = nullptr;
+    int rc = ex_reserve(e, (int64_t)t.tiles_x * t.tiles_y, width, height, channels, &hist, &lut);
+    if (rc) return rc;
+    if ((rc = ex_upload(e, image, ex_in_bytes(width, height, channels, pitch), st))) return rc;
+    if ((rc = ex_clahe_device(e, e.img, pitch, width, height, channels, order, t, hist, lut, st))) return rc;
+    return ex_download(e, width, height, channels, out, out_pitch, st);
+}
+
+int exposure_remap(ExposureBuf& e, const uint8_t* image, int width, int height, int channels, int64_t pitch, int order,
+                   const uint8_t* lut_v_opt, const uint8_t* lut_all_opt, uint8_t* out, int64_t out_pitch, hipStream_t st) {
+    uint32_t* hist = nullptr;
+    uint8_t* lut = nullptr;
+    int rc = ex_reserve(e, 1, width, height, channels, &hist, &lut);
+    if (rc) return rc;
+    if ((rc = ex_upload(e, image, ex_in_bytes(width, height, channels, pitch), st))) return rc;
+    LIO_HIP(hipEventRecord(e.ev[kExLut], st));
+    uint8_t* h_lut = reinterpret_cast<uint8_t*>(e.h_small);
+    std::memset(h_lut, 0, 512);
+    if (lut_v_opt) std::memcpy(h_lut, lut_v_opt, 256);
+    if (lut_all_opt) std::memcpy(h_lut + 256, lut_all_opt, 256);
+    LIO_HIP(hipMemcpyAsync(lut, h_lut, 512, hipMemcpyHostToDevice, st));
+    LIO_HIP(hipEventRecord(e.ev[kExApply], st));
+    ExApplyArg a{};
+    a.W = width, a.H = height, a.order = order, a.tiles_x = 1, a.tiles_y = 1;
+    a.has_v = lut_v_opt != nullptr, a.has_all = lut_all_opt != nullptr;
+    if ((rc = ex_launch_apply<1>(e.img, pitch, channels, a, lut, e.out, st))) return rc;
+    LIO_HIP(hipEventRecord(e.ev[kExDownload], st));
+    return ex_download(e, width, height, channels, out, out_pitch, st);
+}
+
+int exposure_clahe_undistorted(ExposureBuf& e, UndistortBuf& u, const uint8_t* raw, int64_t pitch, int order, const ExTiling& t,
+                               uint8_t* out, int64_t out_pitch, hipStream_t st) {
+    uint32_t* hist = nullptr;
+    uint8_t* lut = nullptr;
+    int rc = ex_reserve(e, (int64_t)t.tiles_x * t.tiles_y, u.dw, u.dh, u.channels, &hist, &lut);
+    if (rc) return rc;
+    // the upload stage here is the undistorter's upload and gather: the rectified frame stays in u.out
+    LIO_HIP(hipEventRecord(e.ev[kExUpload], st));
+    if ((rc = undistorter_rectify(u, raw, pitch, st))) return rc;
+    LIO_HIP(hipEventRecord(e.ev[kExHist], st));
+    if ((rc = ex_clahe_device(e, u.out, ex_pitch(u.dw, u.channels), u.dw, u.dh, u.channels, order, t, hist, lut, st))) return rc;
+    return ex_download(e, u.dw, u.dh, u.channels, out, out_pitch, st);
+}
+
+}  // namespace lio

@@ -1,11 +1,13 @@
 // lio_scratch.hpp — the host-side plumbing every scratch struct shares.  Host only, header only.
 //   status codes, LIO_HIP, nblk(), grown()          every driver
 //   Carver, carve_arena, reserve_arena              the one-arena reserves: DenoiseBuf, ClusterBuf, PlaneBuf (sized by a
-//                                                   capacity the caller keeps), GpsAlignBuf, ProjectBuf (sized per call)
+//                                                   capacity the caller keeps), GpsAlignBuf, ProjectBuf, ExposureBuf (sized
+//                                                   per call)
 //   dev_free, dev_alloc_all, grow_buf, grow_scratch device buffers: FilterBuf, GridBuf, MapUpdBuf, ColorizeBuf,
-//                                                   UndistortBuf and the C-ABI's handles
+//                                                   UndistortBuf, ExposureBuf and the C-ABI's handles
 //   host_free, grow_pinned                          pinned host buffers: the sweep staging (FilterBuf), the image staging
-//                                                   (ColorizeBuf, UndistortBuf), GpsAlignBuf::h_part, DenoiseBuf::h_dist
+//                                                   (ColorizeBuf, UndistortBuf, ExposureBuf), GpsAlignBuf::h_part,
+//                                                   DenoiseBuf::h_dist
 // The hipcub sort / scan pair is in lio_scratch_cub.hpp.
 //
 // The first section needs no HIP header: define LIO_SCRATCH_NO_HIP before the include to get it alone

@@ -201,12 +201,14 @@ int undistorter_set_camera(UndistortBuf& u, const CamArg& src, const UdDst& dst,
     return kOk;
 }
 
-int undistorter_run(UndistortBuf& u, const uint8_t* image, int64_t pitch, uint8_t* out, int64_t out_pitch, hipStream_t st) {
+// the device row pitch of the rectified frame: channels * dw rounded up to 4 bytes
+static int64_t ud_out_pitch(const UndistortBuf& u) { return (int64_t)(((size_t)u.dw * (size_t)u.channels + 3) & ~(size_t)3); }
+
+int undistorter_rectify(UndistortBuf& u, const uint8_t* image, int64_t pitch, hipStream_t st) {
     const int C = u.channels;
     // the last row ends after its channels * width bytes: nothing past it is read from the caller's buffer
     const size_t in_bytes = (size_t)(u.sh - 1) * (size_t)pitch + (size_t)u.sw * (size_t)C;
-    const size_t row_bytes = (size_t)u.dw * (size_t)C;
-    const int64_t d_pitch = (int64_t)((row_bytes + 3) & ~(size_t)3);
+    const int64_t d_pitch = ud_out_pitch(u);
     const size_t out_bytes = (size_t)d_pitch * (size_t)u.dh;
     int rc = grow_pinned(&u.h_img, u.h_img_bytes, in_bytes, kImageStageFloor);
     if (!rc) rc = grow_pinned(&u.h_out, u.h_out_bytes, out_bytes, kImageStageFloor);
@@ -226,6 +228,15 @@ int undistorter_run(UndistortBuf& u, const uint8_t* image, int64_t pitch, uint8_
                                                    u.border);
     LIO_HIP(hipGetLastError());
     LIO_HIP(hipEventRecord(u.ev[2], st));
+    return kOk;
+}
+
+int undistorter_run(UndistortBuf& u, const uint8_t* image, int64_t pitch, uint8_t* out, int64_t out_pitch, hipStream_t st) {
+    const int rc = undistorter_rectify(u, image, pitch, st);
+    if (rc) return rc;
+    const size_t row_bytes = (size_t)u.dw * (size_t)u.channels;
+    const int64_t d_pitch = ud_out_pitch(u);
+    const size_t out_bytes = (size_t)d_pitch * (size_t)u.dh;
     LIO_HIP(hipMemcpyAsync(u.h_out, u.out, out_bytes, hipMemcpyDeviceToHost, st));
     LIO_HIP(hipEventRecord(u.ev[3], st));
     LIO_HIP(hipStreamSynchronize(st));

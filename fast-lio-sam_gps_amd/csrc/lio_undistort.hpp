@@ -54,5 +54,9 @@ int undistorter_set_camera(UndistortBuf& u, const CamArg& src, const UdDst& dst,
 // one frame: image (host, sh rows of `pitch` bytes) -> out (host, dh rows of `out_pitch` bytes, of which
 // channels * dw are written).  Waits for the stream.
 int undistorter_run(UndistortBuf& u, const uint8_t* image, int64_t pitch, uint8_t* out, int64_t out_pitch, hipStream_t st);
+// the first half of undistorter_run, for a caller that goes on with the frame on the device (lio_exposure.hip):
+// upload and gather, enqueued on st and not waited for.  The rectified frame is u.out: dh rows of channels * dw
+// rounded up to 4 bytes.
+int undistorter_rectify(UndistortBuf& u, const uint8_t* image, int64_t pitch, hipStream_t st);
 
 }  // namespace lio

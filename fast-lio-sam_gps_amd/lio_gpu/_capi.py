@@ -61,6 +61,8 @@ EXPORTS = [
     "lio_colorizer_reset", "lio_colorizer_get_timing",
     "lio_undistort_map", "lio_undistorter_create", "lio_undistorter_destroy", "lio_undistorter_set_camera",
     "lio_undistorter_run", "lio_undistorter_get_timing",
+    "lio_exposure_create", "lio_exposure_destroy", "lio_exposure_histograms", "lio_exposure_clahe", "lio_exposure_remap",
+    "lio_exposure_clahe_undistorted", "lio_exposure_get_timing",
 ]
 
 
@@ -266,6 +268,17 @@ def _declare(L):
         "lio_undistorter_set_camera": (C.c_int, [vp, C.POINTER(Camera), C.POINTER(Camera), C.c_int, C.POINTER(C.c_uint8)]),
         "lio_undistorter_run": (C.c_int, [vp, vp, C.c_int64, vp, C.c_int64]),
         "lio_undistorter_get_timing": (C.c_int, [vp, dp]),
+        "lio_exposure_create": (C.c_int, [C.c_int, C.POINTER(vp)]),
+        "lio_exposure_destroy": (C.c_int, [vp]),
+        "lio_exposure_histograms": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.POINTER(C.c_int64),
+                                              C.POINTER(C.c_int64)]),
+        "lio_exposure_clahe": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_double, C.c_int, C.c_int,
+                                         vp, C.c_int64]),
+        "lio_exposure_remap": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.POINTER(C.c_uint8),
+                                         C.POINTER(C.c_uint8), vp, C.c_int64]),
+        "lio_exposure_clahe_undistorted": (C.c_int, [vp, vp, vp, C.c_int64, C.c_int, C.c_double, C.c_int, C.c_int, vp,
+                                                     C.c_int64]),
+        "lio_exposure_get_timing": (C.c_int, [vp, dp]),
         "lio_ctx_create": (C.c_int, [vp, C.POINTER(MatchParams), C.POINTER(vp)]),
         "lio_ctx_destroy": (C.c_int, [vp]),
         "lio_scan_set": (C.c_int, [vp, fp, C.c_int64]),

@@ -908,6 +908,84 @@ int lio_ctx_reset_timing(lio_ctx* c);
 int lio_icp_set_timing(lio_icp* h, int enable);
 int lio_icp_get_timing(lio_icp* h, lio_kernel_timing* out);
 
+/* -------------------------------------------------------- exposure adaption (CLAHE on V, table remaps; camera leg) */
+/* What the reference runs on every rectified frame: post_process/exposure_adaption/CLAHE_region_adjusted.py:6-41
+ * (adapt_exposure: BGR -> HSV, CLAHE of V with clip 2.0 and 8 x 8 tiles, HSV -> BGR) and correct_exposure:6-103
+ * (detect_exposure on the gray histogram, then equalizeHist or a 5..95 percentile stretch of V and a gamma table).
+ * The contract is the library's own, exact to the bit.  All float operations are IEEE float32, rounded one at a
+ * time, in the order written, nothing fused; rint is TIES TO EVEN; sat clamps to 0..255.  AGREEMENT WITH cv2 IS OUR
+ * READING OF ITS SOURCE AND IS UNVERIFIED: OpenCV was not available where this was written.
+ *   images   uint8, channels 1 or 3, width and height in 1..32767, rows of `pitch` bytes.  Only channels x width
+ *            bytes of a row are read or written: the output's padding bytes are left untouched.
+ *   order    0 = B G R (what cv2.imread gives), 1 = R G B.  It only says which byte is r and which is b below; the
+ *            output has the input's order.
+ *   BGR -> HSV  (our reading of OpenCV's 8-bit path, hsv_shift = 12, H range 180, all integer)
+ *            sdiv[i] = rint((255 << 12) / i), hdiv[i] = rint((180 << 12) / (6 i)) for i = 1..255, computed in double;
+ *            sdiv[0] = hdiv[0] = 0.  v = max(b, g, r); vmin = min(b, g, r); d = v - vmin;
+ *            s = (d sdiv[v] + 2048) >> 12;
+ *            h0 = g - b if v == r, else b - r + 2 d if v == g, else r - g + 4 d;
+ *            h = (h0 hdiv[d] + 2048) >> 12 (arithmetic shift); if h < 0, h += 180.  h is in 0..179.
+ *            With 1 channel V is the pixel itself and no conversion is made.
+ *   HSV -> BGR  (our reading of OpenCV's float path behind the 8-bit entry)
+ *            hs = 0x1.111112p-5f (the float nearest 1/30), k = 0x1.010102p-8f (the float nearest 1/255);
+ *            hf = (float)h hs; sf = (float)s k; vf = (float)v k.  If s == 0: b = g = r = vf.  Otherwise
+ *            sec = floor(hf); f = hf - (float)sec; if sec >= 6: sec = 0, f = 0;
+ *            t0 = vf; t1 = vf (1 - sf); t2 = vf (1 - sf f); t3 = vf (1 - sf (1 - f));
+ *            (b, g, r) = t[...] by sector: {1,3,0} {1,0,2} {3,0,1} {0,2,1} {0,1,3} {2,1,0}.
+ *            Each output channel is sat(rint(x 255.0f)).
+ *   CLAHE of a plane  (our reading of OpenCV's clahe.cpp; clip_limit double, tiles_x and tiles_y in 1..64)
+ *     padding  if W % tiles_x == 0 and H % tiles_y == 0 the extended plane is the plane.  Otherwise it is padded on
+ *              the right by tiles_x - W % tiles_x columns and at the bottom by tiles_y - H % tiles_y rows: A DIMENSION
+ *              THAT DIVIDES EVENLY IS THEN PADDED BY A WHOLE tiles_x OR tiles_y (OpenCV's quirk, kept).  The border is
+ *              REFLECT_101: x >= W reads 2 (W - 1) - x.  A pad larger than the dimension - 1 is LIO_ERR_ARG.
+ *     tiles    tw = extW / tiles_x; th = extH / tiles_y; area = tw th.
+ *     clip     clip = 0 if clip_limit <= 0; otherwise clip = max((int)(clip_limit area / 256), 1), computed in double;
+ *              NaN, or a value >= 2^31, is LIO_ERR_ARG.
+ *     per tile a 256-bin histogram of the tile of the extended plane (reflected pixels count).  If clip > 0:
+ *              excess = sum max(hist - clip, 0); hist = min(hist, clip); batch = excess / 256; res = excess - 256
+ *              batch; every bin gains batch; if res > 0: step = max(256 / res, 1) and bin k gets one more iff k % step
+ *              == 0 and k / step < res (the closed form of OpenCV's loop).  lut[i] = sat(rint((float)cum[i] scale)),
+ *              cum the inclusive prefix sum, scale = 255.0f / (float)area.
+ *     apply    per pixel (x, y) of the unpadded plane, p = plane[y][x]:
+ *              txf = (float)x (1.0f / (float)tw) - 0.5f; tx1 = floor(txf); xa = txf - (float)tx1; xa1 = 1 - xa; then
+ *              tx2 = min(tx1 + 1, tiles_x - 1) and tx1 = max(tx1, 0); rows likewise with th;
+ *              res = (L[ty1][tx1][p] xa1 + L[ty1][tx2][p] xa) ya1 + (L[ty2][tx1][p] xa1 + L[ty2][tx2][p] xa) ya;
+ *              out = sat(rint(res)).
+ *   gray     (detect_exposure only; our reading of OpenCV 4's 15-bit path)
+ *            gray = (3735 b + 19235 g + 9798 r + 16384) >> 15.
+ * The script's v / 255 -> clip -> * 255 -> uint8 step in float32 is the identity on 0..255 and is not performed.
+ *
+ * lio_exposure_histograms: 256 int64 each (either may be NULL): hist_v of V (the channel maximum; with 1 channel the
+ *   plane), hist_gray of gray (with 1 channel the plane).
+ * lio_exposure_clahe: 1 channel: CLAHE of the plane.  3 channels: adapt_exposure: BGR -> HSV, CLAHE of V, H and S
+ *   unchanged, HSV -> BGR.
+ * lio_exposure_remap: 3 channels with lut_v: the HSV round trip with V = lut_v[V]; then, if lut_all is given, every
+ *   channel goes through it (the gamma step).  lut_v NULL: no round trip, a plain cv2.LUT.  1 channel: lut_v, then
+ *   lut_all, on the plane.  Each table is 256 uint8.  Both NULL is LIO_ERR_ARG.
+ * lio_exposure_clahe_undistorted: the undistorter's configured frame is rectified and adapted with ONE UPLOAD AND ONE
+ *   DOWNLOAD; the result equals lio_undistorter_run followed by lio_exposure_clahe bit for bit.  Both handles must
+ *   be on one device (LIO_ERR_ARG); LIO_ERR_STATE before lio_undistorter_set_camera.  The undistorter must not be in
+ *   use by another thread meanwhile.
+ * lio_exposure_get_timing: device ms of the last run from stream events: upload (its staging copy included; in the
+ *   chained call the undistorter's upload and gather), histogram, LUT, apply, download.
+ * LIO_ERR_ARG before any device work, with a message that names the bound: a NULL image, out, raw_image or ms5, a
+ * width or height outside 1..32767, channels not 1 or 3, order not 0 or 1, tiles_x or tiles_y outside 1..64, pitch or
+ * out_pitch < channels x width, the padding bound and the clip bounds above, both tables NULL.  The checks that need
+ * no handle are made before the handle is looked at.  There is no CPU path: LIO_ERR_NODEV without a device.  From the
+ * second frame of one size on nothing is allocated (lio_alloc_count); repeated runs give identical bits.          */
+typedef struct lio_exposure lio_exposure;
+int lio_exposure_create(int device, lio_exposure** out);
+int lio_exposure_destroy(lio_exposure* h);
+int lio_exposure_histograms(lio_exposure* h, const uint8_t* image, int width, int height, int channels, int64_t pitch,
+                            int order, int64_t* hist_v_opt, int64_t* hist_gray_opt);
+int lio_exposure_clahe(lio_exposure* h, const uint8_t* image, int width, int height, int channels, int64_t pitch, int order,
+                       double clip_limit, int tiles_x, int tiles_y, uint8_t* out, int64_t out_pitch);
+int lio_exposure_remap(lio_exposure* h, const uint8_t* image, int width, int height, int channels, int64_t pitch, int order,
+                       const uint8_t* lut_v_opt, const uint8_t* lut_all_opt, uint8_t* out, int64_t out_pitch);
+int lio_exposure_clahe_undistorted(lio_exposure* h, lio_undistorter* undistorter, const uint8_t* raw_image, int64_t pitch,
+                                   int order, double clip_limit, int tiles_x, int tiles_y, uint8_t* out, int64_t out_pitch);
+int lio_exposure_get_timing(lio_exposure* h, double* ms5);
+
 #ifdef __cplusplus
 }
 #endif

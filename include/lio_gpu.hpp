@@ -929,10 +929,159 @@ public:
         check(lio_undistorter_get_timing(h_, ms.data()), "Undistorter::timing");
         return ms;
     }
+    // for Exposure::claheUndistorted: the handle, and the channels and widths of the last setCamera
+    lio_undistorter* handle() const { return h_; }
+    int channels() const { return channels_; }
+    int rawWidth() const { return sw_; }
+    int width() const { return dw_; }
 
 private:
     lio_undistorter* h_ = nullptr;
     int sw_ = 0, dw_ = 0, channels_ = 3;
+};
+
+// The host side of the reference's correct_exposure (post_process/exposure_adaption/correct_exposure:6-70): 256-entry
+// tables from a 256-bin histogram, as lio_gpu.exposure has them.  hist: 256 counts, not all zero.
+using ExposureLut = std::array<uint8_t, 256>;
+using ExposureHist = std::array<int64_t, 256>;
+
+namespace detail {
+inline uint8_t sat_rint_f32(float x) {
+    const float r = std::nearbyint(x);  // the default rounding mode: ties to even
+    return (uint8_t)(r < 0.f ? 0.f : (r > 255.f ? 255.f : r));
+}
+inline int64_t hist_total(const ExposureHist& hist, const char* what) {
+    int64_t n = 0;
+    for (int64_t c : hist) {
+        if (c < 0) throw Error(LIO_ERR_ARG, std::string(what) + ": a negative count");
+        n += c;
+    }
+    if (n < 1) throw Error(LIO_ERR_ARG, std::string(what) + ": the histogram is empty");
+    return n;
+}
+}  // namespace detail
+
+// our reading of cv2.equalizeHist: i0 the first non-empty bin; if it holds every pixel everything maps to i0;
+// otherwise scale = 255.0f / (float)(total - hist[i0]), lut[i <= i0] = 0, lut[i] = sat(rint((float)sum * scale))
+inline ExposureLut equalize_lut(const ExposureHist& hist) {
+    const int64_t total = detail::hist_total(hist, "equalize_lut");
+    size_t i0 = 0;
+    while (hist[i0] == 0) ++i0;
+    ExposureLut lut{};
+    if (hist[i0] == total) {
+        lut.fill((uint8_t)i0);
+        return lut;
+    }
+    const float scale = 255.0f / (float)(total - hist[i0]);
+    int64_t sum = 0;
+    for (size_t i = i0 + 1; i < 256; ++i) {
+        sum += hist[i];
+        lut[i] = detail::sat_rint_f32((float)sum * scale);
+    }
+    return lut;
+}
+
+// np.percentile(plane, q) (linear) from the plane's histogram: position (n - 1) * (q / 100), numpy's interpolation
+inline double hist_percentile(const ExposureHist& hist, double q) {
+    const int64_t n = detail::hist_total(hist, "hist_percentile");
+    double pos = (double)(n - 1) * (q / 100.0);
+    pos = pos < 0.0 ? 0.0 : (pos > (double)(n - 1) ? (double)(n - 1) : pos);
+    const int64_t lo = (int64_t)std::floor(pos), hi = lo + 1 < n ? lo + 1 : n - 1;
+    const double t = pos - (double)lo;
+    double a = 0.0, b = 0.0;
+    int64_t cum = 0;
+    bool have_a = false;
+    for (int v = 0; v < 256; ++v) {  // the sorted plane's values at the indices lo and hi
+        cum += hist[(size_t)v];
+        if (!have_a && cum > lo) a = v, have_a = true;
+        if (cum > hi) {
+            b = v;
+            break;
+        }
+    }
+    const double d = b - a;
+    return t >= 0.5 ? b - d * (1.0 - t) : a + d * t;
+}
+
+// correct_exposure:59-61: lut[v] = uint8(clip((v - lo) / (hi - lo) * 255, 0, 255)) in double, truncating
+inline ExposureLut stretch_lut(const ExposureHist& hist, double lo_pct = 5.0, double hi_pct = 95.0) {
+    const double lo = hist_percentile(hist, lo_pct), hi = hist_percentile(hist, hi_pct);
+    if (hi == lo) throw Error(LIO_ERR_ARG, "stretch_lut: the two percentiles are equal");
+    ExposureLut lut{};
+    for (int v = 0; v < 256; ++v) {
+        const double x = ((double)v - lo) / (hi - lo) * 255.0;
+        lut[(size_t)v] = (uint8_t)(x < 0.0 ? 0.0 : (x > 255.0 ? 255.0 : x));
+    }
+    return lut;
+}
+
+// correct_exposure:48, 69: uint8(clip((x / 255.0) ** gamma * 255.0, 0, 255)) in double
+inline ExposureLut gamma_lut(double gamma) {
+    ExposureLut lut{};
+    for (int v = 0; v < 256; ++v) {
+        const double x = std::pow((double)v / 255.0, gamma) * 255.0;
+        lut[(size_t)v] = (uint8_t)(x < 0.0 ? 0.0 : (x > 255.0 ? 255.0 : x));
+    }
+    return lut;
+}
+
+// correct_exposure:19-30 on the gray histogram: 1 overexposed, -1 underexposed, 0 well-exposed
+inline int detect_exposure(const ExposureHist& hist_gray) {
+    const double total = (double)detail::hist_total(hist_gray, "detect_exposure");
+    int64_t low = 0, high = 0;
+    for (size_t i = 0; i < 50; ++i) low += hist_gray[i];
+    for (size_t i = 200; i < 256; ++i) high += hist_gray[i];
+    if ((double)high / total > 0.3) return 1;
+    if ((double)low / total > 0.3) return -1;
+    return 0;
+}
+
+// Exposure adaption of frames (lio_exposure): histograms, CLAHE of V (CLAHE_region_adjusted.py's adapt_exposure with the
+// defaults), table remaps, and the undistorter's frame adapted on the device.  Images: rows of `pitch` bytes (0:
+// channels * width); order 0 = B G R, 1 = R G B.
+class Exposure {
+public:
+    explicit Exposure(int device = 0) { check(lio_exposure_create(device, &h_), "lio_exposure_create"); }
+    ~Exposure() { lio_exposure_destroy(h_); }
+    Exposure(const Exposure&) = delete;
+    Exposure& operator=(const Exposure&) = delete;
+    void histograms(const uint8_t* image, int width, int height, int channels, ExposureHist* hist_v, ExposureHist* hist_gray,
+                    int order = 0, int64_t pitch = 0) {
+        check(lio_exposure_histograms(h_, image, width, height, channels, pitch ? pitch : (int64_t)channels * width, order,
+                                      hist_v ? hist_v->data() : nullptr, hist_gray ? hist_gray->data() : nullptr),
+              "Exposure::histograms");
+    }
+    void clahe(const uint8_t* image, int width, int height, int channels, uint8_t* out, double clip_limit = 2.0, int tiles_x = 8,
+               int tiles_y = 8, int order = 0, int64_t pitch = 0, int64_t out_pitch = 0) {
+        check(lio_exposure_clahe(h_, image, width, height, channels, pitch ? pitch : (int64_t)channels * width, order, clip_limit,
+                                 tiles_x, tiles_y, out, out_pitch ? out_pitch : (int64_t)channels * width),
+              "Exposure::clahe");
+    }
+    // lut_v on V (the HSV round trip), then lut_all on every channel; either may be null, not both
+    void remap(const uint8_t* image, int width, int height, int channels, const ExposureLut* lut_v, const ExposureLut* lut_all,
+               uint8_t* out, int order = 0, int64_t pitch = 0, int64_t out_pitch = 0) {
+        check(lio_exposure_remap(h_, image, width, height, channels, pitch ? pitch : (int64_t)channels * width, order,
+                                 lut_v ? lut_v->data() : nullptr, lut_all ? lut_all->data() : nullptr, out,
+                                 out_pitch ? out_pitch : (int64_t)channels * width),
+              "Exposure::remap");
+    }
+    // ud.undistort(raw) then clahe, bit for bit, with one upload and one download
+    void claheUndistorted(Undistorter& ud, const uint8_t* raw, uint8_t* out, double clip_limit = 2.0, int tiles_x = 8,
+                          int tiles_y = 8, int order = 0, int64_t pitch = 0, int64_t out_pitch = 0) {
+        check(lio_exposure_clahe_undistorted(h_, ud.handle(), raw, pitch ? pitch : (int64_t)ud.channels() * ud.rawWidth(), order,
+                                             clip_limit, tiles_x, tiles_y, out,
+                                             out_pitch ? out_pitch : (int64_t)ud.channels() * ud.width()),
+              "Exposure::claheUndistorted");
+    }
+    // device ms of the last run: upload, histogram, LUT, apply, download
+    std::array<double, 5> timing() {
+        std::array<double, 5> ms{};
+        check(lio_exposure_get_timing(h_, ms.data()), "Exposure::timing");
+        return ms;
+    }
+
+private:
+    lio_exposure* h_ = nullptr;
 };
 
 // Open3D's PointCloud::SegmentPlane as the offline pipeline calls it (post_process/clustering.py:21-28), in the
