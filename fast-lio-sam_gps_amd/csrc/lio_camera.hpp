@@ -1,6 +1,6 @@
 // lio_camera.hpp — what the camera leg's two halves share on the host (lio_colorize.hpp, lio_undistort.hpp): the
 // camera a kernel is handed, and the arena of the two one-shot entries on a lio_filter.  The device side of the
-// model is lio_camera_dev.hpp.
+// model is lio_camera_dev.hpp, the host path of a frame lio_frame.hpp.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -22,8 +22,5 @@ struct ProjectBuf {
     size_t arena_bytes = 0;
 };
 void project_free(ProjectBuf& b);
-
-// floor of the pinned image staging of the colorizer and of the undistorter (grow_pinned)
-constexpr size_t kImageStageFloor = (size_t)1 << 20;
 
 }  // namespace lio

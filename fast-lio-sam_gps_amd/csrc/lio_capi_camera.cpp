@@ -9,6 +9,31 @@
 
 using namespace lio::capi;
 
+// ---- what the three frame handles share ----
+// The tail of a create: the buffers' init, and a handle whose init fails is closed again: *out stays NULL.
+template <class H, class Init>
+static int init_handle(H** out, const char* what, Init&& init, int (*destroy)(H*)) {
+    const int rc = status(init(**out), what);
+    if (rc) {
+        destroy(*out);
+        *out = nullptr;
+    }
+    return rc;
+}
+
+// the body of a get_timing, after its NULL checks
+template <int N>
+static int stage_times(const lio::StageTimer<N>& t, double* ms) {
+    for (int k = 0; k < N; ++k) ms[k] = t.ms[k];
+    return LIO_OK;
+}
+
+// `name` (pitch or out_pitch) holds a row of the image; `of`: which image, where the call has two
+static int pitch_arg(const std::string& what, const char* name, int64_t pitch, int channels, int width, const char* of = "") {
+    if (pitch >= (int64_t)channels * width) return LIO_OK;
+    return fail(LIO_ERR_ARG, what + ": " + name + " must be at least channels x width bytes" + of);
+}
+
 extern "C" {
 
 // ---- the camera of both halves ----
@@ -91,7 +116,8 @@ int lio_colorizer_destroy(lio_colorizer* h) {
     return close_handle(h, [](lio_colorizer& z) { lio::colorizer_free(z.c); });
 }
 
-// a handle whose params or init fail is closed again: *out stays NULL
+// a handle whose params or init fail is closed again: *out stays NULL.  Written out: the params come before the
+// init, and *out is NULL before the handle is closed.
 int lio_colorizer_create(int device, const lio_colorize_params* params, lio_colorizer** out) {
     int rc = open_handle(device, out, "lio_colorizer_create: out is NULL");
     if (rc) return rc;
@@ -161,8 +187,7 @@ int lio_colorizer_get_timing(lio_colorizer* h, double* ms4) {
     int rc = null_handle(h, "lio_colorizer_get_timing");
     if (rc) return rc;
     if (!ms4) return fail(LIO_ERR_ARG, "lio_colorizer_get_timing: ms4 is NULL");
-    for (int k = 0; k < lio::kCzStages; ++k) ms4[k] = h->c.ms[k];
-    return LIO_OK;
+    return stage_times(h->c.timer, ms4);
 }
 
 // ---- image undistortion (lio_undistort.hip) ----
@@ -206,13 +231,10 @@ int lio_undistorter_destroy(lio_undistorter* h) {
 }
 
 int lio_undistorter_create(int device, lio_undistorter** out) {
-    int rc = open_handle(device, out, "lio_undistorter_create: out is NULL");
+    const int rc = open_handle(device, out, "lio_undistorter_create: out is NULL");
     if (rc) return rc;
-    if ((rc = status(lio::undistorter_init((*out)->u), "lio_undistorter_create"))) {
-        lio_undistorter_destroy(*out);
-        *out = nullptr;
-    }
-    return rc;
+    return init_handle(out, "lio_undistorter_create", [](lio_undistorter& z) { return lio::undistorter_init(z.u); },
+                       lio_undistorter_destroy);
 }
 
 int lio_undistorter_set_camera(lio_undistorter* h, const lio_camera* src, const lio_camera* dst_opt, int channels,
@@ -229,17 +251,20 @@ int lio_undistorter_set_camera(lio_undistorter* h, const lio_camera* src, const 
     return status(lio::undistorter_set_camera(h->u, a, d, channels, border_opt ? border_opt : black, h->st), what);
 }
 
+// a frame through a configured undistorter: the checks lio_undistorter_run and lio_exposure_clahe_undistorted share
+static int undistorter_frame_arg(const std::string& what, const lio::UndistortBuf& u, int64_t pitch, int64_t out_pitch) {
+    if (!u.have_camera) return fail(LIO_ERR_STATE, what + ": no camera (call lio_undistorter_set_camera first)");
+    if (const int rc = pitch_arg(what, "pitch", pitch, u.channels, u.sw, " of the raw image")) return rc;
+    return pitch_arg(what, "out_pitch", out_pitch, u.channels, u.dw, " of the rectified image");
+}
+
 int lio_undistorter_run(lio_undistorter* h, const uint8_t* image, int64_t pitch, uint8_t* out, int64_t out_pitch) {
     const std::string what = "lio_undistorter_run";
     if (!image) return fail(LIO_ERR_ARG, what + ": image is NULL");
     if (!out) return fail(LIO_ERR_ARG, what + ": out is NULL");
-    const int rc = null_handle(h, what.c_str());
+    int rc = null_handle(h, what.c_str());
     if (rc) return rc;
-    if (!h->u.have_camera) return fail(LIO_ERR_STATE, what + ": no camera (call lio_undistorter_set_camera first)");
-    if (pitch < (int64_t)h->u.channels * h->u.sw)
-        return fail(LIO_ERR_ARG, what + ": pitch must be at least channels x width bytes of the raw image");
-    if (out_pitch < (int64_t)h->u.channels * h->u.dw)
-        return fail(LIO_ERR_ARG, what + ": out_pitch must be at least channels x width bytes of the rectified image");
+    if ((rc = undistorter_frame_arg(what, h->u, pitch, out_pitch))) return rc;
     HIP_TRY(hipSetDevice(h->dev));
     return status(lio::undistorter_run(h->u, image, pitch, out, out_pitch, h->st), what.c_str());
 }
@@ -248,8 +273,7 @@ int lio_undistorter_get_timing(lio_undistorter* h, double* ms3) {
     const int rc = null_handle(h, "lio_undistorter_get_timing");
     if (rc) return rc;
     if (!ms3) return fail(LIO_ERR_ARG, "lio_undistorter_get_timing: ms3 is NULL");
-    for (int k = 0; k < lio::kUdStages; ++k) ms3[k] = h->u.ms[k];
-    return LIO_OK;
+    return stage_times(h->u.timer, ms3);
 }
 
 // ---- exposure adaption (lio_exposure.hip) ----
@@ -263,10 +287,8 @@ static int exposure_image_arg(const std::string& what, const void* image, int wi
         return fail(LIO_ERR_ARG, what + ": width and height must be in 1..32767");
     if (channels != 1 && channels != 3) return fail(LIO_ERR_ARG, what + ": channels must be 1 or 3");
     if (order != 0 && order != 1) return fail(LIO_ERR_ARG, what + ": order must be 0 (B G R) or 1 (R G B)");
-    if (pitch < (int64_t)channels * width) return fail(LIO_ERR_ARG, what + ": pitch must be at least channels x width bytes");
-    if (has_out && out_pitch < (int64_t)channels * width)
-        return fail(LIO_ERR_ARG, what + ": out_pitch must be at least channels x width bytes");
-    return LIO_OK;
+    if (const int rc = pitch_arg(what, "pitch", pitch, channels, width)) return rc;
+    return has_out ? pitch_arg(what, "out_pitch", out_pitch, channels, width) : LIO_OK;
 }
 
 static int exposure_tiles_arg(const std::string& what, int tiles_x, int tiles_y) {
@@ -291,13 +313,9 @@ int lio_exposure_destroy(lio_exposure* h) {
 }
 
 int lio_exposure_create(int device, lio_exposure** out) {
-    int rc = open_handle(device, out, "lio_exposure_create: out is NULL");
+    const int rc = open_handle(device, out, "lio_exposure_create: out is NULL");
     if (rc) return rc;
-    if ((rc = status(lio::exposure_init((*out)->e), "lio_exposure_create"))) {
-        lio_exposure_destroy(*out);
-        *out = nullptr;
-    }
-    return rc;
+    return init_handle(out, "lio_exposure_create", [](lio_exposure& z) { return lio::exposure_init(z.e); }, lio_exposure_destroy);
 }
 
 int lio_exposure_histograms(lio_exposure* h, const uint8_t* image, int width, int height, int channels, int64_t pitch,
@@ -350,11 +368,7 @@ int lio_exposure_clahe_undistorted(lio_exposure* h, lio_undistorter* undistorter
     if (!undistorter) return fail(LIO_ERR_ARG, what + ": undistorter is NULL");
     if (undistorter->dev != h->dev) return fail(LIO_ERR_ARG, what + ": both handles must be on one device");
     const lio::UndistortBuf& u = undistorter->u;
-    if (!u.have_camera) return fail(LIO_ERR_STATE, what + ": no camera (call lio_undistorter_set_camera first)");
-    if (pitch < (int64_t)u.channels * u.sw)
-        return fail(LIO_ERR_ARG, what + ": pitch must be at least channels x width bytes of the raw image");
-    if (out_pitch < (int64_t)u.channels * u.dw)
-        return fail(LIO_ERR_ARG, what + ": out_pitch must be at least channels x width bytes of the rectified image");
+    if ((rc = undistorter_frame_arg(what, u, pitch, out_pitch))) return rc;
     lio::ExTiling t{};
     if ((rc = exposure_tiling_arg(what, u.dw, u.dh, clip_limit, tiles_x, tiles_y, &t))) return rc;
     HIP_TRY(hipSetDevice(h->dev));
@@ -367,8 +381,7 @@ int lio_exposure_get_timing(lio_exposure* h, double* ms5) {
     if (!ms5) return fail(LIO_ERR_ARG, "lio_exposure_get_timing: ms5 is NULL");
     const int rc = null_handle(h, "lio_exposure_get_timing");
     if (rc) return rc;
-    for (int k = 0; k < lio::kExStages; ++k) ms5[k] = h->e.ms[k];
-    return LIO_OK;
+    return stage_times(h->e.timer, ms5);
 }
 
 }  // extern "C"

@@ -16,7 +16,6 @@
 // the pixel already holds a depth that is not larger: the depth image only ever decreases, so a skipped atomic
 // would have changed nothing (a stale read only costs an atomic that changes nothing).
 #include <algorithm>
-#include <cstring>
 
 #include "lio_camera_dev.hpp"
 #include "lio_colorize.hpp"
@@ -189,15 +188,15 @@ int colorizer_init(ColorizeBuf& c) {
     if (hipMalloc(reinterpret_cast<void**>(&c.count), sizeof(unsigned long long)) != hipSuccess) return kNoMem;
     if (hipHostMalloc(reinterpret_cast<void**>(&c.h_count), sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess)
         return kNoMem;
-    for (hipEvent_t& e : c.ev) LIO_HIP(hipEventCreate(&e));
+    LIO_HIP(c.timer.init());
     return kOk;
 }
 
 void colorizer_free(ColorizeBuf& c) {
-    dev_free(&c.pts, &c.best_z, &c.rgb, &c.frame, &c.img, &c.depth, &c.count);
-    host_free(&c.h_img, &c.h_count);
-    for (hipEvent_t e : c.ev)
-        if (e) (void)hipEventDestroy(e);
+    dev_free(&c.pts, &c.best_z, &c.rgb, &c.frame, &c.depth, &c.count);
+    host_free(&c.h_count);
+    c.in.free();
+    c.timer.free();
     c = ColorizeBuf{};
 }
 
@@ -234,39 +233,34 @@ int colorizer_set_cloud(ColorizeBuf& c, const float* pts, int64_t n, int stride,
 
 int colorizer_add_frame(ColorizeBuf& c, const CamArg& cam, const uint8_t* image, int64_t pitch, bool bgr, bool occlusion,
                         int splat_radius, float depth_rel, float depth_abs, int64_t* n_updated, hipStream_t st) {
-    // the last row ends after its 3 * width bytes: nothing past it is read from the caller's buffer
-    const size_t bytes = (size_t)(cam.height - 1) * (size_t)pitch + (size_t)cam.width * 3;
+    const size_t bytes = frame_span(cam.height, pitch, (size_t)cam.width * 3);
     const int64_t pixels = (int64_t)cam.width * cam.height;
     const int64_t pixels4 = (pixels + 3) / 4;
-    int rc = grow_pinned(&c.h_img, c.h_img_bytes, bytes, kImageStageFloor);
-    if (!rc) rc = grow_scratch(reinterpret_cast<void**>(&c.img), c.img_bytes, bytes);
+    int rc = reserve_frames({{&c.in, bytes}});
     if (!rc && occlusion) rc = grow_buf(&c.depth, c.depth_cap, pixels4 * 4);
     if (rc) return rc;
     const int32_t frame_no = c.frames;
-    LIO_HIP(hipEventRecord(c.ev[0], st));
-    std::memcpy(c.h_img, image, bytes);
-    LIO_HIP(hipMemcpyAsync(c.img, c.h_img, bytes, hipMemcpyHostToDevice, st));
+    LIO_HIP(c.timer.mark(kCzUpload, st));
+    LIO_HIP(c.in.upload(image, bytes, st));
     LIO_HIP(hipMemsetAsync(c.count, 0, sizeof(unsigned long long), st));
-    LIO_HIP(hipEventRecord(c.ev[1], st));
+    LIO_HIP(c.timer.mark(kCzFill, st));
     if (occlusion && c.n > 0) {
         cz_fill_kernel<<<nblk(pixels4), 256, 0, st>>>(reinterpret_cast<uint4*>(c.depth), pixels4, kCzInfBits);
-        LIO_HIP(hipEventRecord(c.ev[2], st));
+        LIO_HIP(c.timer.mark(kCzSplat, st));
         cz_splat_kernel<<<nblk(c.n), 256, 0, st>>>(c.pts, c.n, c.stride, cam, splat_radius, c.depth);
-        LIO_HIP(hipEventRecord(c.ev[3], st));
-        cz_resolve_kernel<<<nblk(c.n), 256, 0, st>>>(c.pts, c.n, c.stride, cam, c.depth, depth_rel, depth_abs, c.img, pitch,
+        LIO_HIP(c.timer.mark(kCzResolve, st));
+        cz_resolve_kernel<<<nblk(c.n), 256, 0, st>>>(c.pts, c.n, c.stride, cam, c.depth, depth_rel, depth_abs, c.in.dev, pitch,
                                                      bgr, frame_no, c.best_z, c.rgb, c.frame, c.count);
     } else {
-        LIO_HIP(hipEventRecord(c.ev[2], st));
-        LIO_HIP(hipEventRecord(c.ev[3], st));
+        LIO_HIP(c.timer.mark(kCzSplat, kCzResolve, st));  // no fill, no splat
         if (c.n > 0)
-            cz_fused_kernel<<<nblk(c.n), 256, 0, st>>>(c.pts, c.n, c.stride, cam, c.img, pitch, bgr, frame_no, c.best_z,
+            cz_fused_kernel<<<nblk(c.n), 256, 0, st>>>(c.pts, c.n, c.stride, cam, c.in.dev, pitch, bgr, frame_no, c.best_z,
                                                        c.rgb, c.frame, c.count);
     }
     LIO_HIP(hipGetLastError());
-    LIO_HIP(hipEventRecord(c.ev[kCzStages], st));
+    LIO_HIP(c.timer.mark(kCzStages, st));
     LIO_HIP(hipMemcpyAsync(c.h_count, c.count, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    LIO_HIP(hipStreamSynchronize(st));
-    for (int k = 0; k < kCzStages; ++k) LIO_HIP(hipEventElapsedTime(&c.ms[k], c.ev[k], c.ev[k + 1]));
+    LIO_HIP(c.timer.finish(st));
     c.frames = frame_no + 1;
     *n_updated = (int64_t)*c.h_count;
     return kOk;

@@ -8,13 +8,14 @@
 #include <stdint.h>
 
 #include "lio_camera.hpp"
+#include "lio_frame.hpp"
 
 namespace lio {
 
 constexpr int kCzMaxSplat = 8;               // the largest splat radius
 constexpr uint32_t kCzInfBits = 0x7f800000u;  // bits of float +inf: an empty depth pixel
 
-// stages of colorizer_add_frame, for ColorizeBuf::ms (event times of the last frame)
+// stages of colorizer_add_frame, for ColorizeBuf::timer (event times of the last frame)
 enum CzStage { kCzUpload = 0, kCzFill = 1, kCzSplat = 2, kCzResolve = 3, kCzStages = 4 };
 
 // records (device, n x stride) -> uv (n x 2 doubles), zc (n doubles), pix (n x 2 int32, -1 where invalid), valid
@@ -33,17 +34,13 @@ struct ColorizeBuf {
     uint8_t* rgb = nullptr;    // n x 3
     int32_t* frame = nullptr;  // n
     int64_t state_cap = 0;     // points
-    uint8_t* img = nullptr;    // the frame's image as uploaded (rows of `pitch` bytes)
-    size_t img_bytes = 0;
-    uint8_t* h_img = nullptr;  // pinned staging of the image
-    size_t h_img_bytes = 0;
+    FrameStage in;             // the frame's image as uploaded (rows of `pitch` bytes)
     uint32_t* depth = nullptr;  // width x height, a multiple of 4 words
     int64_t depth_cap = 0;
     unsigned long long* count = nullptr;    // the frame's replacements
     unsigned long long* h_count = nullptr;  // pinned: its host copy
     int32_t frames = 0;                     // the running frame number
-    hipEvent_t ev[kCzStages + 1] = {};
-    float ms[kCzStages] = {};
+    StageTimer<kCzStages> timer;
 };
 int colorizer_init(ColorizeBuf& c);
 void colorizer_free(ColorizeBuf& c);

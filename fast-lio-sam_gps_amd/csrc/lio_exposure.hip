@@ -20,7 +20,6 @@
 //                    with MODE 1 is the table remap of lio_exposure_remap.
 #include <cstring>
 
-#include "lio_camera.hpp"
 #include "lio_exposure.hpp"
 #include "lio_scratch.hpp"
 
@@ -276,37 +275,25 @@ __global__ __launch_bounds__(256) void ex_apply_kernel(const uint8_t* __restrict
     }
 }
 
-// the device row pitch of a result: channels * width rounded up to 4 bytes
-int64_t ex_pitch(int width, int channels) { return (int64_t)(((size_t)width * (size_t)channels + 3) & ~(size_t)3); }
-
-size_t ex_in_bytes(int width, int height, int channels, int64_t pitch) {
-    // the last row ends after its channels * width bytes: nothing past it is read from the caller's buffer
-    return (size_t)(height - 1) * (size_t)pitch + (size_t)width * (size_t)channels;
-}
-
-// everything a run of `tiles` tiles needs besides the input, reserved before anything is enqueued: the arena
-// (hist, lut), the result and its staging
-int ex_reserve(ExposureBuf& e, int64_t tiles, int width, int height, int channels, uint32_t** hist, uint8_t** lut) {
+// everything a run of `tiles` tiles needs, reserved before anything is enqueued: the arena (hist, lut), the result
+// of out_height rows (0: the run returns no image), then the input (in_bytes 0: the frame is on the device already)
+int ex_reserve(ExposureBuf& e, int64_t tiles, size_t in_bytes, int width, int out_height, int channels, uint32_t** hist,
+               uint8_t** lut) {
     auto fields = [&](Carver& c) {
         c(*hist, (size_t)tiles * 256);
         c(*lut, (size_t)std::max<int64_t>(tiles, 2) * 256);
     };
     int rc = reserve_arena(&e.arena, e.arena_bytes, fields);
-    const size_t out_bytes = (size_t)ex_pitch(width, channels) * (size_t)height;
-    if (!rc && out_bytes) rc = grow_pinned(&e.h_out, e.h_out_bytes, out_bytes, kImageStageFloor);
-    if (!rc && out_bytes) rc = grow_scratch(reinterpret_cast<void**>(&e.out), e.out_bytes, out_bytes);
+    if (!rc) rc = reserve_frames({{&e.out, (size_t)frame_pitch(width, channels) * (size_t)out_height}});
+    if (!rc) rc = reserve_frames({{&e.in, in_bytes}});
     return rc;
 }
 
-// ev[0] .. ev[1]: the frame into e.img
+// the upload stage: the frame into e.in
 int ex_upload(ExposureBuf& e, const uint8_t* image, size_t in_bytes, hipStream_t st) {
-    int rc = grow_pinned(&e.h_img, e.h_img_bytes, in_bytes, kImageStageFloor);
-    if (!rc) rc = grow_scratch(reinterpret_cast<void**>(&e.img), e.img_bytes, in_bytes);
-    if (rc) return rc;
-    LIO_HIP(hipEventRecord(e.ev[kExUpload], st));
-    std::memcpy(e.h_img, image, in_bytes);
-    LIO_HIP(hipMemcpyAsync(e.img, e.h_img, in_bytes, hipMemcpyHostToDevice, st));
-    LIO_HIP(hipEventRecord(e.ev[kExHist], st));
+    LIO_HIP(e.timer.mark(kExUpload, st));
+    LIO_HIP(e.in.upload(image, in_bytes, st));
+    LIO_HIP(e.timer.mark(kExHist, st));
     return kOk;
 }
 
@@ -329,7 +316,7 @@ template <int MODE>
 int ex_launch_apply(const uint8_t* d_img, int64_t pitch, int channels, const ExApplyArg& a, const uint8_t* lut, uint8_t* out,
                     hipStream_t st) {
     const dim3 block(64, 4), grid((unsigned)((a.W + 255) / 256), (unsigned)((a.H + 3) / 4));
-    const int64_t out_pitch = ex_pitch(a.W, channels);
+    const int64_t out_pitch = frame_pitch(a.W, channels);
     if (channels == 3)
         ex_apply_kernel<3, MODE><<<grid, block, 0, st>>>(d_img, pitch, a, lut, out, out_pitch);
     else
@@ -338,39 +325,21 @@ int ex_launch_apply(const uint8_t* d_img, int64_t pitch, int channels, const ExA
     return kOk;
 }
 
-// ev[1] .. ev[4]: histograms, tables and the apply of the device image into e.out
+// the stages kExHist .. kExApply: histograms, tables and the apply of the device image into e.out
 int ex_clahe_device(ExposureBuf& e, const uint8_t* d_img, int64_t pitch, int width, int height, int channels, int order,
                     const ExTiling& t, uint32_t* hist, uint8_t* lut, hipStream_t st) {
     int rc = ex_launch_hist(d_img, pitch, width, height, channels, order, 0, t.tiles_x, t.tiles_y, t.tw, t.th, hist, st);
     if (rc) return rc;
-    LIO_HIP(hipEventRecord(e.ev[kExLut], st));
+    LIO_HIP(e.timer.mark(kExLut, st));
     const float scale = 255.0f / (float)(t.tw * t.th);
     ex_lut_kernel<<<t.tiles_x * t.tiles_y, 256, 0, st>>>(hist, t.clip, scale, lut);
     LIO_HIP(hipGetLastError());
-    LIO_HIP(hipEventRecord(e.ev[kExApply], st));
+    LIO_HIP(e.timer.mark(kExApply, st));
     ExApplyArg a{};
     a.W = width, a.H = height, a.order = order, a.tiles_x = t.tiles_x, a.tiles_y = t.tiles_y;
     a.inv_tw = 1.0f / (float)t.tw, a.inv_th = 1.0f / (float)t.th;
-    if ((rc = ex_launch_apply<0>(d_img, pitch, channels, a, lut, e.out, st))) return rc;
-    LIO_HIP(hipEventRecord(e.ev[kExDownload], st));
-    return kOk;
-}
-
-// ev[4] .. ev[5]: e.out to the caller's rows, channels * width bytes each (its padding is not touched); the wait
-// and the stage times
-int ex_download(ExposureBuf& e, int width, int height, int channels, uint8_t* out, int64_t out_pitch, hipStream_t st) {
-    const size_t row_bytes = (size_t)width * (size_t)channels;
-    const int64_t d_pitch = ex_pitch(width, channels);
-    const size_t out_bytes = (size_t)d_pitch * (size_t)height;
-    LIO_HIP(hipMemcpyAsync(e.h_out, e.out, out_bytes, hipMemcpyDeviceToHost, st));
-    LIO_HIP(hipEventRecord(e.ev[kExStages], st));
-    LIO_HIP(hipStreamSynchronize(st));
-    for (int k = 0; k < kExStages; ++k) LIO_HIP(hipEventElapsedTime(&e.ms[k], e.ev[k], e.ev[k + 1]));
-    if (out_pitch == d_pitch && row_bytes == (size_t)d_pitch)
-        std::memcpy(out, e.h_out, out_bytes);
-    else
-        for (int i = 0; i < height; ++i)
-            std::memcpy(out + (size_t)i * (size_t)out_pitch, e.h_out + (size_t)i * (size_t)d_pitch, row_bytes);
+    if ((rc = ex_launch_apply<0>(d_img, pitch, channels, a, lut, e.out.dev, st))) return rc;
+    LIO_HIP(e.timer.mark(kExDownload, st));
     return kOk;
 }
 
@@ -402,15 +371,16 @@ int exposure_tiling(int width, int height, double clip_limit, int tiles_x, int t
 }
 
 int exposure_init(ExposureBuf& e) {
-    for (hipEvent_t& ev : e.ev) LIO_HIP(hipEventCreate(&ev));
+    LIO_HIP(e.timer.init());
     return grow_pinned(&e.h_small, e.h_small_bytes, 2 * 256 * sizeof(uint32_t), 0);
 }
 
 void exposure_free(ExposureBuf& e) {
-    dev_free(&e.img, &e.out, &e.arena);
-    host_free(&e.h_img, &e.h_out, &e.h_small);
-    for (hipEvent_t ev : e.ev)
-        if (ev) (void)hipEventDestroy(ev);
+    dev_free(&e.arena);
+    host_free(&e.h_small);
+    e.in.free();
+    e.out.free();
+    e.timer.free();
     e = ExposureBuf{};
 }
 
@@ -418,19 +388,19 @@ int exposure_histograms(ExposureBuf& e, const uint8_t* image, int width, int hei
                         int64_t* hist_v_opt, int64_t* hist_gray_opt, hipStream_t st) {
     uint32_t* hist = nullptr;
     uint8_t* lut = nullptr;
-    int rc = ex_reserve(e, 2, 0, 0, channels, &hist, &lut);  // two 1 x 1 tilings: V, then gray
+    const size_t in_bytes = frame_span(height, pitch, (size_t)width * (size_t)channels);
+    int rc = ex_reserve(e, 2, in_bytes, width, 0, channels, &hist, &lut);  // two 1 x 1 tilings: V, then gray
     if (rc) return rc;
-    if ((rc = ex_upload(e, image, ex_in_bytes(width, height, channels, pitch), st))) return rc;
-    if (hist_v_opt && (rc = ex_launch_hist(e.img, pitch, width, height, channels, order, 0, 1, 1, width, height, hist, st)))
+    if ((rc = ex_upload(e, image, in_bytes, st))) return rc;
+    if (hist_v_opt && (rc = ex_launch_hist(e.in.dev, pitch, width, height, channels, order, 0, 1, 1, width, height, hist, st)))
         return rc;
     if (hist_gray_opt &&
-        (rc = ex_launch_hist(e.img, pitch, width, height, channels, order, 1, 1, 1, width, height, hist + 256, st)))
+        (rc = ex_launch_hist(e.in.dev, pitch, width, height, channels, order, 1, 1, 1, width, height, hist + 256, st)))
         return rc;
-    for (int k = kExLut; k <= kExDownload; ++k) LIO_HIP(hipEventRecord(e.ev[k], st));
+    LIO_HIP(e.timer.mark(kExLut, kExDownload, st));  // no tables, no apply
     LIO_HIP(hipMemcpyAsync(e.h_small, hist, 2 * 256 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    LIO_HIP(hipEventRecord(e.ev[kExStages], st));
-    LIO_HIP(hipStreamSynchronize(st));
-    for (int k = 0; k < kExStages; ++k) LIO_HIP(hipEventElapsedTime(&e.ms[k], e.ev[k], e.ev[k + 1]));
+    LIO_HIP(e.timer.mark(kExStages, st));
+    LIO_HIP(e.timer.finish(st));
     for (int i = 0; i < 256; ++i) {
         if (hist_v_opt) hist_v_opt[i] = (int64_t)e.h_small[i];
         if (hist_gray_opt) hist_gray_opt[i] = (int64_t)e.h_small[256 + i];
@@ -442,47 +412,50 @@ int exposure_clahe(ExposureBuf& e, const uint8_t* image, int width, int height, 
                    const ExTiling& t, uint8_t* out, int64_t out_pitch, hipStream_t st) {
     uint32_t* hist = nullptr;
     uint8_t* lut = nullptr;
-    int rc = ex_reserve(e, (int64_t)t.tiles_x * t.tiles_y, width, height, channels, &hist, &lut);
+    const size_t in_bytes = frame_span(height, pitch, (size_t)width * (size_t)channels);
+    int rc = ex_reserve(e, (int64_t)t.tiles_x * t.tiles_y, in_bytes, width, height, channels, &hist, &lut);
     if (rc) return rc;
-    if ((rc = ex_upload(e, image, ex_in_bytes(width, height, channels, pitch), st))) return rc;
-    if ((rc = ex_clahe_device(e, e.img, pitch, width, height, channels, order, t, hist, lut, st))) return rc;
-    return ex_download(e, width, height, channels, out, out_pitch, st);
+    if ((rc = ex_upload(e, image, in_bytes, st))) return rc;
+    if ((rc = ex_clahe_device(e, e.in.dev, pitch, width, height, channels, order, t, hist, lut, st))) return rc;
+    return download_frame(e.out, e.timer, width, height, channels, out, out_pitch, st);
 }
 
 int exposure_remap(ExposureBuf& e, const uint8_t* image, int width, int height, int channels, int64_t pitch, int order,
                    const uint8_t* lut_v_opt, const uint8_t* lut_all_opt, uint8_t* out, int64_t out_pitch, hipStream_t st) {
     uint32_t* hist = nullptr;
     uint8_t* lut = nullptr;
-    int rc = ex_reserve(e, 1, width, height, channels, &hist, &lut);
+    const size_t in_bytes = frame_span(height, pitch, (size_t)width * (size_t)channels);
+    int rc = ex_reserve(e, 1, in_bytes, width, height, channels, &hist, &lut);
     if (rc) return rc;
-    if ((rc = ex_upload(e, image, ex_in_bytes(width, height, channels, pitch), st))) return rc;
-    LIO_HIP(hipEventRecord(e.ev[kExLut], st));
+    if ((rc = ex_upload(e, image, in_bytes, st))) return rc;
+    LIO_HIP(e.timer.mark(kExLut, st));
     uint8_t* h_lut = reinterpret_cast<uint8_t*>(e.h_small);
     std::memset(h_lut, 0, 512);
     if (lut_v_opt) std::memcpy(h_lut, lut_v_opt, 256);
     if (lut_all_opt) std::memcpy(h_lut + 256, lut_all_opt, 256);
     LIO_HIP(hipMemcpyAsync(lut, h_lut, 512, hipMemcpyHostToDevice, st));
-    LIO_HIP(hipEventRecord(e.ev[kExApply], st));
+    LIO_HIP(e.timer.mark(kExApply, st));
     ExApplyArg a{};
     a.W = width, a.H = height, a.order = order, a.tiles_x = 1, a.tiles_y = 1;
     a.has_v = lut_v_opt != nullptr, a.has_all = lut_all_opt != nullptr;
-    if ((rc = ex_launch_apply<1>(e.img, pitch, channels, a, lut, e.out, st))) return rc;
-    LIO_HIP(hipEventRecord(e.ev[kExDownload], st));
-    return ex_download(e, width, height, channels, out, out_pitch, st);
+    if ((rc = ex_launch_apply<1>(e.in.dev, pitch, channels, a, lut, e.out.dev, st))) return rc;
+    LIO_HIP(e.timer.mark(kExDownload, st));
+    return download_frame(e.out, e.timer, width, height, channels, out, out_pitch, st);
 }
 
 int exposure_clahe_undistorted(ExposureBuf& e, UndistortBuf& u, const uint8_t* raw, int64_t pitch, int order, const ExTiling& t,
                                uint8_t* out, int64_t out_pitch, hipStream_t st) {
     uint32_t* hist = nullptr;
     uint8_t* lut = nullptr;
-    int rc = ex_reserve(e, (int64_t)t.tiles_x * t.tiles_y, u.dw, u.dh, u.channels, &hist, &lut);
+    int rc = ex_reserve(e, (int64_t)t.tiles_x * t.tiles_y, 0, u.dw, u.dh, u.channels, &hist, &lut);
     if (rc) return rc;
-    // the upload stage here is the undistorter's upload and gather: the rectified frame stays in u.out
-    LIO_HIP(hipEventRecord(e.ev[kExUpload], st));
+    // the upload stage here is the undistorter's upload and gather: the rectified frame stays in u.out.dev
+    LIO_HIP(e.timer.mark(kExUpload, st));
     if ((rc = undistorter_rectify(u, raw, pitch, st))) return rc;
-    LIO_HIP(hipEventRecord(e.ev[kExHist], st));
-    if ((rc = ex_clahe_device(e, u.out, ex_pitch(u.dw, u.channels), u.dw, u.dh, u.channels, order, t, hist, lut, st))) return rc;
-    return ex_download(e, u.dw, u.dh, u.channels, out, out_pitch, st);
+    LIO_HIP(e.timer.mark(kExHist, st));
+    if ((rc = ex_clahe_device(e, u.out.dev, frame_pitch(u.dw, u.channels), u.dw, u.dh, u.channels, order, t, hist, lut, st)))
+        return rc;
+    return download_frame(e.out, e.timer, u.dw, u.dh, u.channels, out, out_pitch, st);
 }
 
 }  // namespace lio

@@ -13,7 +13,7 @@ namespace lio {
 constexpr int kExMaxSize = kUdMaxSize;  // the largest width or height, as for the undistorter
 constexpr int kExMaxTiles = 64;         // tiles per direction
 
-// stages of a run, for ExposureBuf::ms (event times of the last run)
+// stages of a run, for ExposureBuf::timer (event times of the last run)
 enum ExStage { kExUpload = 0, kExHist = 1, kExLut = 2, kExApply = 3, kExDownload = 4, kExStages = 5 };
 
 // the tiling of a plane: the extended size, the tile size and the clip value of the contract.  exposure_tiling
@@ -28,20 +28,13 @@ int exposure_tiling(int width, int height, double clip_limit, int tiles_x, int t
 
 // the state of a lio_exposure: the staging of one frame, the histograms and the tables
 struct ExposureBuf {
-    uint8_t* img = nullptr;  // the frame as uploaded (rows of the caller's pitch)
-    size_t img_bytes = 0;
-    uint8_t* out = nullptr;  // the result: rows of channels * width rounded up to 4 bytes
-    size_t out_bytes = 0;
-    uint8_t* h_img = nullptr;  // pinned staging of both
-    size_t h_img_bytes = 0;
-    uint8_t* h_out = nullptr;
-    size_t h_out_bytes = 0;
+    FrameStage in;   // the frame as uploaded (rows of the caller's pitch)
+    FrameStage out;  // the result: rows of frame_pitch(width, channels) bytes
     void* arena = nullptr;  // uint32 hist[tiles][256], then uint8 lut[tiles][256] (remap: lut_v, lut_all)
     size_t arena_bytes = 0;
     uint32_t* h_small = nullptr;  // pinned, 2 x 256 uint32: the histograms down, the two tables up
     size_t h_small_bytes = 0;
-    hipEvent_t ev[kExStages + 1] = {};
-    float ms[kExStages] = {};
+    StageTimer<kExStages> timer;
 };
 int exposure_init(ExposureBuf& e);
 void exposure_free(ExposureBuf& e);

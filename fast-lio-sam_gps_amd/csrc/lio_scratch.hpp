@@ -4,10 +4,11 @@
 //                                                   capacity the caller keeps), GpsAlignBuf, ProjectBuf, ExposureBuf (sized
 //                                                   per call)
 //   dev_free, dev_alloc_all, grow_buf, grow_scratch device buffers: FilterBuf, GridBuf, MapUpdBuf, ColorizeBuf,
-//                                                   UndistortBuf, ExposureBuf and the C-ABI's handles
+//                                                   UndistortBuf, ExposureBuf, FrameStage and the C-ABI's handles
 //   host_free, grow_pinned                          pinned host buffers: the sweep staging (FilterBuf), the image staging
-//                                                   (ColorizeBuf, UndistortBuf, ExposureBuf), GpsAlignBuf::h_part,
-//                                                   DenoiseBuf::h_dist
+//                                                   (FrameStage in lio_frame.hpp, which ColorizeBuf, UndistortBuf and
+//                                                   ExposureBuf hold), GpsAlignBuf::h_part, DenoiseBuf::h_dist,
+//                                                   ExposureBuf::h_small
 // The hipcub sort / scan pair is in lio_scratch_cub.hpp.
 //
 // The first section needs no HIP header: define LIO_SCRATCH_NO_HIP before the include to get it alone

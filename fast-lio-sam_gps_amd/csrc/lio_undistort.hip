@@ -14,8 +14,6 @@
 //                    over bytes everywhere); 4 * channels bytes out as dwords.  The device's own output rows are a
 //                    multiple of 4 bytes, so every full group of a row is dword-aligned whatever pitch the caller's
 //                    buffer has; only the last, partial group of a row goes out as bytes.  Nothing is staged in LDS.
-#include <cstring>
-
 #include "lio_camera_dev.hpp"
 #include "lio_scratch.hpp"
 #include "lio_undistort.hpp"
@@ -174,15 +172,15 @@ int undistort_map(ProjectBuf& b, const CamArg& src, const UdDst& dst, double* uv
 }
 
 int undistorter_init(UndistortBuf& u) {
-    for (hipEvent_t& e : u.ev) LIO_HIP(hipEventCreate(&e));
+    LIO_HIP(u.timer.init());
     return kOk;
 }
 
 void undistorter_free(UndistortBuf& u) {
-    dev_free(&u.map, &u.img, &u.out);
-    host_free(&u.h_img, &u.h_out);
-    for (hipEvent_t e : u.ev)
-        if (e) (void)hipEventDestroy(e);
+    dev_free(&u.map);
+    u.in.free();
+    u.out.free();
+    u.timer.free();
     u = UndistortBuf{};
 }
 
@@ -201,52 +199,31 @@ int undistorter_set_camera(UndistortBuf& u, const CamArg& src, const UdDst& dst,
     return kOk;
 }
 
-// the device row pitch of the rectified frame: channels * dw rounded up to 4 bytes
-static int64_t ud_out_pitch(const UndistortBuf& u) { return (int64_t)(((size_t)u.dw * (size_t)u.channels + 3) & ~(size_t)3); }
-
 int undistorter_rectify(UndistortBuf& u, const uint8_t* image, int64_t pitch, hipStream_t st) {
     const int C = u.channels;
-    // the last row ends after its channels * width bytes: nothing past it is read from the caller's buffer
-    const size_t in_bytes = (size_t)(u.sh - 1) * (size_t)pitch + (size_t)u.sw * (size_t)C;
-    const int64_t d_pitch = ud_out_pitch(u);
-    const size_t out_bytes = (size_t)d_pitch * (size_t)u.dh;
-    int rc = grow_pinned(&u.h_img, u.h_img_bytes, in_bytes, kImageStageFloor);
-    if (!rc) rc = grow_pinned(&u.h_out, u.h_out_bytes, out_bytes, kImageStageFloor);
-    if (!rc) rc = grow_scratch(reinterpret_cast<void**>(&u.img), u.img_bytes, in_bytes);
-    if (!rc) rc = grow_scratch(reinterpret_cast<void**>(&u.out), u.out_bytes, out_bytes);
+    const size_t in_bytes = frame_span(u.sh, pitch, (size_t)u.sw * (size_t)C);
+    const int64_t d_pitch = frame_pitch(u.dw, C);
+    const int rc = reserve_frames({{&u.in, in_bytes}, {&u.out, (size_t)d_pitch * (size_t)u.dh}});
     if (rc) return rc;
-    LIO_HIP(hipEventRecord(u.ev[0], st));
-    std::memcpy(u.h_img, image, in_bytes);
-    LIO_HIP(hipMemcpyAsync(u.img, u.h_img, in_bytes, hipMemcpyHostToDevice, st));
-    LIO_HIP(hipEventRecord(u.ev[1], st));
+    LIO_HIP(u.timer.mark(kUdUpload, st));
+    LIO_HIP(u.in.upload(image, in_bytes, st));
+    LIO_HIP(u.timer.mark(kUdKernel, st));
     const dim3 block(64, 4), grid((unsigned)((u.dw + 255) / 256), (unsigned)((u.dh + 3) / 4));
     if (C == 3)
-        ud_remap_kernel<3><<<grid, block, 0, st>>>(u.img, pitch, u.sw, u.sh, u.map, u.map_pitch, u.dw, u.dh, u.out, d_pitch,
-                                                   u.border);
+        ud_remap_kernel<3><<<grid, block, 0, st>>>(u.in.dev, pitch, u.sw, u.sh, u.map, u.map_pitch, u.dw, u.dh, u.out.dev,
+                                                   d_pitch, u.border);
     else
-        ud_remap_kernel<1><<<grid, block, 0, st>>>(u.img, pitch, u.sw, u.sh, u.map, u.map_pitch, u.dw, u.dh, u.out, d_pitch,
-                                                   u.border);
+        ud_remap_kernel<1><<<grid, block, 0, st>>>(u.in.dev, pitch, u.sw, u.sh, u.map, u.map_pitch, u.dw, u.dh, u.out.dev,
+                                                   d_pitch, u.border);
     LIO_HIP(hipGetLastError());
-    LIO_HIP(hipEventRecord(u.ev[2], st));
+    LIO_HIP(u.timer.mark(kUdDownload, st));
     return kOk;
 }
 
 int undistorter_run(UndistortBuf& u, const uint8_t* image, int64_t pitch, uint8_t* out, int64_t out_pitch, hipStream_t st) {
     const int rc = undistorter_rectify(u, image, pitch, st);
     if (rc) return rc;
-    const size_t row_bytes = (size_t)u.dw * (size_t)u.channels;
-    const int64_t d_pitch = ud_out_pitch(u);
-    const size_t out_bytes = (size_t)d_pitch * (size_t)u.dh;
-    LIO_HIP(hipMemcpyAsync(u.h_out, u.out, out_bytes, hipMemcpyDeviceToHost, st));
-    LIO_HIP(hipEventRecord(u.ev[3], st));
-    LIO_HIP(hipStreamSynchronize(st));
-    for (int k = 0; k < kUdStages; ++k) LIO_HIP(hipEventElapsedTime(&u.ms[k], u.ev[k], u.ev[k + 1]));
-    // the caller's rows: channels * width bytes each, its padding is not touched
-    if (out_pitch == d_pitch && row_bytes == (size_t)d_pitch)
-        std::memcpy(out, u.h_out, out_bytes);
-    else
-        for (int i = 0; i < u.dh; ++i) std::memcpy(out + (size_t)i * (size_t)out_pitch, u.h_out + (size_t)i * (size_t)d_pitch, row_bytes);
-    return kOk;
+    return download_frame(u.out, u.timer, u.dw, u.dh, u.channels, out, out_pitch, st);
 }
 
 }  // namespace lio

@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "lio_camera.hpp"
+#include "lio_frame.hpp"
 
 namespace lio {
 
@@ -19,7 +20,7 @@ struct UdDst {
     int32_t width, height;
 };
 
-// stages of undistorter_run, for UndistortBuf::ms (event times of the last frame)
+// stages of undistorter_run, for UndistortBuf::timer (event times of the last frame)
 enum UdStage { kUdUpload = 0, kUdKernel = 1, kUdDownload = 2, kUdStages = 3 };
 
 // lio_undistort_map on a lio_filter: dst.height x dst.width x 2 values to each HOST pointer given (any may be
@@ -35,16 +36,9 @@ struct UndistortBuf {
     int sw = 0, sh = 0, dw = 0, dh = 0, channels = 0;
     uint32_t border = 0;  // channel c in bits 8c .. 8c + 7
     bool have_camera = false;
-    uint8_t* img = nullptr;  // the frame as uploaded (rows of the caller's pitch)
-    size_t img_bytes = 0;
-    uint8_t* out = nullptr;  // the rectified frame: rows of out_pitch bytes (channels * dw rounded up to 4)
-    size_t out_bytes = 0;
-    uint8_t* h_img = nullptr;  // pinned staging of both
-    size_t h_img_bytes = 0;
-    uint8_t* h_out = nullptr;
-    size_t h_out_bytes = 0;
-    hipEvent_t ev[kUdStages + 1] = {};
-    float ms[kUdStages] = {};
+    FrameStage in;   // the frame as uploaded (rows of the caller's pitch)
+    FrameStage out;  // the rectified frame: rows of frame_pitch(dw, channels) bytes
+    StageTimer<kUdStages> timer;
 };
 int undistorter_init(UndistortBuf& u);
 void undistorter_free(UndistortBuf& u);
@@ -55,8 +49,8 @@ int undistorter_set_camera(UndistortBuf& u, const CamArg& src, const UdDst& dst,
 // channels * dw are written).  Waits for the stream.
 int undistorter_run(UndistortBuf& u, const uint8_t* image, int64_t pitch, uint8_t* out, int64_t out_pitch, hipStream_t st);
 // the first half of undistorter_run, for a caller that goes on with the frame on the device (lio_exposure.hip):
-// upload and gather, enqueued on st and not waited for.  The rectified frame is u.out: dh rows of channels * dw
-// rounded up to 4 bytes.
+// upload and gather, enqueued on st and not waited for.  The rectified frame is u.out.dev: dh rows of
+// frame_pitch(dw, channels) bytes.
 int undistorter_rectify(UndistortBuf& u, const uint8_t* image, int64_t pitch, hipStream_t st);
 
 }  // namespace lio

@@ -131,11 +131,7 @@ def _image(image, camera: CameraModel):
     a = np.asarray(image)
     if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
         raise ValueError("image: a height x width x 3 uint8 array is expected")
-    if a.shape[:2] != (camera.height, camera.width):
-        raise ValueError(f"image: shape {a.shape[:2]} is not the camera's (height, width) = {(camera.height, camera.width)}")
-    if a.strides[2] != 1 or a.strides[1] != 3 or a.strides[0] < 3 * camera.width:
-        a = np.ascontiguousarray(a)
-    return a, a.strides[0]
+    return _plane(a, camera.width, camera.height)[:2]
 
 
 def _plane(image, width: int, height: int, what: str = "image"):
@@ -154,6 +150,19 @@ def _plane(image, width: int, height: int, what: str = "image"):
     return a, a.strides[0], ch
 
 
+def _out(out, shape, ch, width):
+    """(the array to return, the view handed to the library) of a result of ``shape``: ``out`` or a new array; its
+    rows may be padded, its pixels not"""
+    if out is None:
+        out = np.empty(shape, np.uint8)
+    if not isinstance(out, np.ndarray) or out.dtype != np.uint8 or out.shape != shape or not out.flags.writeable:
+        raise ValueError(f"out: a writeable uint8 array of shape {shape} is expected")
+    o = out[:, :, 0] if (out.ndim == 3 and ch == 1) else out
+    if o.strides[-1] != 1 or o.strides[1] != ch or o.strides[0] < ch * width:
+        raise ValueError("out: the pixels of a row must be packed (rows may be padded)")
+    return out, o
+
+
 def undistort_map(src: CameraModel, dst: CameraModel | None = None, handle: _Handle | None = None):
     """The map of ``lio_undistort_map`` from the raw camera ``src`` to the rectified camera ``dst`` (none: ``src``'s
     intrinsics and size): ``(uv, sxy, axy)``, each ``height x width x 2`` of ``dst``: the unquantised source
@@ -170,26 +179,16 @@ def undistort_map(src: CameraModel, dst: CameraModel | None = None, handle: _Han
     return uv, sxy, axy
 
 
-class Undistorter:
+class Undistorter(_Handle):
     """``cv2.undistort(img, K, D, None, K)`` per frame: ``set_camera`` once (the map stays on the device), then call
     the handle on every image.  Bilinear in 1/32 pixel with a constant ``border`` per tap, by the contract of
     include/lio_gpu.h (agreement with OpenCV is a reading of its source, not a test)."""
 
+    _create, _destroy = "lio_undistorter_create", "lio_undistorter_destroy"
+
     def __init__(self, device: int = 0):
-        self._h = C.c_void_p()
         self._shape = None  # (src height, src width, dst height, dst width, channels)
-        check(lib().lio_undistorter_create(device, C.byref(self._h)))
-
-    def close(self):
-        if self._h:
-            lib().lio_undistorter_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().__init__(device)
 
     def set_camera(self, camera: CameraModel, new_camera: CameraModel | None = None, channels: int = 3, border=(0, 0, 0)):
         """``camera``: the raw image's; ``new_camera``: the rectified image's pinhole (none: ``camera.rectified()``, the
@@ -215,22 +214,14 @@ class Undistorter:
         if c != ch:
             raise ValueError(f"image: {c} channel(s), the handle was set up for {ch}")
         shape = (dh, dw) if np.ndim(image) == 2 else (dh, dw, ch)
-        if out is None:
-            out = np.empty(shape, np.uint8)
-        if not isinstance(out, np.ndarray) or out.dtype != np.uint8 or out.shape != shape or not out.flags.writeable:
-            raise ValueError(f"out: a writeable uint8 array of shape {shape} is expected")
-        o = out[:, :, 0] if (out.ndim == 3 and ch == 1) else out
-        if o.strides[-1] != 1 or o.strides[1] != ch or o.strides[0] < ch * dw:
-            raise ValueError("out: the pixels of a row must be packed (rows may be padded)")
+        out, o = _out(out, shape, ch, dw)
         check(lib().lio_undistorter_run(self._h, img.ctypes.data_as(C.c_void_p), pitch, o.ctypes.data_as(C.c_void_p),
                                         o.strides[0]))
         return out
 
     def timing(self) -> dict:
         """device ms of the last frame: upload (staging copy included), kernel, download"""
-        ms = np.zeros(3, np.float64)
-        check(lib().lio_undistorter_get_timing(self._h, ms.ctypes.data_as(_dp)))
-        return dict(zip(("upload_ms", "kernel_ms", "download_ms"), (float(v) for v in ms)))
+        return self._timing("lio_undistorter_get_timing", ("upload_ms", "kernel_ms", "download_ms"))
 
 
 def undistort_image(image, camera: CameraModel, new_camera: CameraModel | None = None, border=(0, 0, 0)) -> np.ndarray:
@@ -244,7 +235,7 @@ def undistort_image(image, camera: CameraModel, new_camera: CameraModel | None =
         ud.close()
 
 
-class Colorizer:
+class Colorizer(_Handle):
     """Colours of a cloud from camera frames: ``set_cloud`` once, ``add_frame`` per image; per point the nearest
     view wins (the smallest depth ``zc``; on a tie the earlier frame).  ``occlusion=False`` is the reference
     (colorize_pcd.py has none: points behind a wall take the wall's colour); ``occlusion=True`` builds a z-buffer
@@ -252,23 +243,13 @@ class Colorizer:
     point only if ``zf <= D * (1 + depth_rel) + depth_abs`` at its own pixel.  ``bgr``: the image's channel order is
     OpenCV's (as in the script); the state is always R G B."""
 
+    _create, _destroy = "lio_colorizer_create", "lio_colorizer_destroy"
+
     def __init__(self, occlusion: bool = False, splat_radius: int = 0, depth_rel: float = 0.0, depth_abs: float = 0.0,
                  bgr: bool = True, device: int = 0):
-        self._h = C.c_void_p()
         self._n = 0
         p = _capi.ColorizeParams(int(bool(occlusion)), int(splat_radius), float(depth_rel), float(depth_abs), int(bool(bgr)))
-        check(lib().lio_colorizer_create(device, C.byref(p), C.byref(self._h)))
-
-    def close(self):
-        if self._h:
-            lib().lio_colorizer_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().__init__(device, C.byref(p))
 
     def set_params(self, occlusion: bool = False, splat_radius: int = 0, depth_rel: float = 0.0, depth_abs: float = 0.0,
                    bgr: bool = True):
@@ -322,9 +303,7 @@ class Colorizer:
 
     def timing(self) -> dict:
         """device ms of the last frame: upload (staging copy included), fill, splat, resolve (or the fused kernel)"""
-        ms = np.zeros(4, np.float64)
-        check(lib().lio_colorizer_get_timing(self._h, ms.ctypes.data_as(_dp)))
-        return dict(zip(("upload_ms", "fill_ms", "splat_ms", "resolve_ms"), (float(v) for v in ms)))
+        return self._timing("lio_colorizer_get_timing", ("upload_ms", "fill_ms", "splat_ms", "resolve_ms"))
 
 
 def colors_float(rgb, frame) -> np.ndarray:

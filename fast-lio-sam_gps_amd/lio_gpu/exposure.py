@@ -18,9 +18,9 @@ import ctypes as C
 import numpy as np
 
 from ._capi import check, lib
-from .camera import _plane
+from .camera import _out, _plane
+from .filters import _Handle
 
-_dp = C.POINTER(C.c_double)
 _i64p = C.POINTER(C.c_int64)
 _u8p = C.POINTER(C.c_uint8)
 BGR, RGB = 0, 1
@@ -112,36 +112,11 @@ def _table(lut, name):
     return a, a.ctypes.data_as(_u8p)
 
 
-def _out(out, shape, ch, width):
-    """(the array to return, the view handed to the library) — as Undistorter: rows may be padded, pixels not"""
-    if out is None:
-        out = np.empty(shape, np.uint8)
-    if not isinstance(out, np.ndarray) or out.dtype != np.uint8 or out.shape != shape or not out.flags.writeable:
-        raise ValueError(f"out: a writeable uint8 array of shape {shape} is expected")
-    o = out[:, :, 0] if (out.ndim == 3 and ch == 1) else out
-    if o.strides[-1] != 1 or o.strides[1] != ch or o.strides[0] < ch * width:
-        raise ValueError("out: the pixels of a row must be packed (rows may be padded)")
-    return out, o
-
-
-class Exposure:
+class Exposure(_Handle):
     """One handle for the exposure work on frames of any size: the staging is reused across frames.  ``order``:
     :data:`BGR` (0, OpenCV's) or :data:`RGB` (1); the output has the input's order."""
 
-    def __init__(self, device: int = 0):
-        self._h = C.c_void_p()
-        check(lib().lio_exposure_create(device, C.byref(self._h)))
-
-    def close(self):
-        if self._h:
-            lib().lio_exposure_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    _create, _destroy = "lio_exposure_create", "lio_exposure_destroy"
 
     @staticmethod
     def _image(image):
@@ -202,9 +177,7 @@ class Exposure:
 
     def timing(self) -> dict:
         """device ms of the last run: upload (staging copy included), histogram, LUT, apply, download"""
-        ms = np.zeros(5, np.float64)
-        check(lib().lio_exposure_get_timing(self._h, ms.ctypes.data_as(_dp)))
-        return dict(zip(("upload_ms", "hist_ms", "lut_ms", "apply_ms", "download_ms"), (float(v) for v in ms)))
+        return self._timing("lio_exposure_get_timing", ("upload_ms", "hist_ms", "lut_ms", "apply_ms", "download_ms"))
 
 
 # ------------------------------------------------------------------------------------------ the scripts' functions

@@ -34,14 +34,24 @@ def _fp(a):
 
 
 class _Handle:
-    def __init__(self, device: int = 0):
+    """A handle of the C-ABI: a ``lio_filter``, or what a subclass names in ``_create`` / ``_destroy`` (``args``: what
+    its create takes between ``device`` and ``out``)."""
+    _create, _destroy = "lio_filter_create", "lio_filter_destroy"
+
+    def __init__(self, device: int = 0, *args):
         self._h = C.c_void_p()
-        check(lib().lio_filter_create(device, C.byref(self._h)))
+        check(getattr(lib(), self._create)(device, *args, C.byref(self._h)))
 
     def close(self):
         if self._h:
-            lib().lio_filter_destroy(self._h)
+            getattr(lib(), self._destroy)(self._h)
             self._h = C.c_void_p()
+
+    def _timing(self, fn: str, names) -> dict:
+        """``names`` -> the device ms of the last call's stages, from the handle's ``get_timing``"""
+        ms = np.zeros(len(names), np.float64)
+        check(getattr(lib(), fn)(self._h, ms.ctypes.data_as(C.POINTER(C.c_double))))
+        return dict(zip(names, (float(v) for v in ms)))
 
     def __del__(self):
         try:

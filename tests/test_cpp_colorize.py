@@ -27,8 +27,18 @@ def test_cpp_colorize_compiles_and_links(tmp_path):
 
 
 def test_makefile_builds_the_driver():
-    mk = open(os.path.join(ROOT, "fast-lio-sam_gps_amd", "Makefile")).read()
-    assert mk.count("$(OUTDIR)/colorize_api") >= 3 and "csrc/lio_colorize.hip" in mk  # all, its rule, clean
+    """`all` reaches the driver's rule (g++ with -Werror on tests/cpp/colorize_api.cpp) and the kernels' object, and
+    `clean` removes the driver: read from make's own dry run, whatever way the Makefile spells its rules"""
+    def dry(goal):
+        r = subprocess.run(["make", "-n", "-B", "-C", os.path.join(ROOT, "fast-lio-sam_gps_amd"), goal], capture_output=True,
+                           text=True, timeout=60)
+        assert r.returncode == 0, r.stderr[-2000:]
+        return r.stdout
+    built = dry("all")
+    rule = [line for line in built.splitlines() if "../tests/cpp/colorize_api.cpp" in line]
+    assert len(rule) == 1 and rule[0].startswith("g++ ") and "-Werror" in rule[0] and "-o lio_gpu/_lib/colorize_api" in rule[0]
+    assert "csrc/lio_colorize.hip" in built
+    assert "lio_gpu/_lib/colorize_api" in dry("clean")
 
 
 @pytest.mark.gpu

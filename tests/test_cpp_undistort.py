@@ -38,8 +38,18 @@ def test_cpp_undistort_compiles_and_links(exe):
 
 
 def test_makefile_builds_the_driver():
-    mk = open(os.path.join(ROOT, "fast-lio-sam_gps_amd", "Makefile")).read()
-    assert mk.count("$(OUTDIR)/undistort_api") >= 3 and "csrc/lio_undistort.hip" in mk  # all, its rule, clean
+    """`all` reaches the driver's rule (g++ with -Werror on tests/cpp/undistort_api.cpp) and the kernels' object, and
+    `clean` removes the driver: read from make's own dry run, whatever way the Makefile spells its rules"""
+    def dry(goal):
+        r = subprocess.run(["make", "-n", "-B", "-C", os.path.join(ROOT, "fast-lio-sam_gps_amd"), goal], capture_output=True,
+                           text=True, timeout=60)
+        assert r.returncode == 0, r.stderr[-2000:]
+        return r.stdout
+    built = dry("all")
+    rule = [line for line in built.splitlines() if "../tests/cpp/undistort_api.cpp" in line]
+    assert len(rule) == 1 and rule[0].startswith("g++ ") and "-Werror" in rule[0] and "-o lio_gpu/_lib/undistort_api" in rule[0]
+    assert "csrc/lio_undistort.hip" in built
+    assert "lio_gpu/_lib/undistort_api" in dry("clean")
 
 
 def write_scene(path, scene, channels, border, img_rows, pitch, out_pitch):
