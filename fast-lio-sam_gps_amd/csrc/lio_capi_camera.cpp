@@ -5,6 +5,7 @@
 #include "lio_capi_util.hpp"
 #include "lio_colorize.hpp"
 #include "lio_exposure.hpp"
+#include "lio_overexposure.hpp"
 #include "lio_undistort.hpp"
 
 using namespace lio::capi;
@@ -382,6 +383,88 @@ int lio_exposure_get_timing(lio_exposure* h, double* ms5) {
     const int rc = null_handle(h, "lio_exposure_get_timing");
     if (rc) return rc;
     return stage_times(h->e.timer, ms5);
+}
+
+// ---- overexposure recovery and the 8-bit Gaussian blur (lio_overexposure.hip) ----
+// The kernel's size and sigma; they need no device.
+static int gaussian_arg(const std::string& what, int ksize, double sigma) {
+    if (ksize < 1 || ksize > lio::kOxMaxKsize || ksize % 2 == 0) return fail(LIO_ERR_ARG, what + ": ksize must be odd and in 1..31");
+    if (!all_finite(&sigma, 1)) return fail(LIO_ERR_ARG, what + ": sigma must be finite");
+    return LIO_OK;
+}
+
+// p_opt NULL: the script's 200 / 5 / 15 / 0.  Fills the weights.
+static int recover_arg(const std::string& what, const lio_recover_params* p_opt, lio::OxRecover* p) {
+    double sigma = 0.0;
+    if (p_opt) {
+        p->threshold = p_opt->threshold, p->dilate = p_opt->dilate, p->ksize = p_opt->ksize;
+        sigma = p_opt->sigma;
+    }
+    if (p->threshold < 0 || p->threshold > 255) return fail(LIO_ERR_ARG, what + ": threshold must be in 0..255");
+    if (p->dilate < 1 || p->dilate > lio::kOxMaxDilate || p->dilate % 2 == 0)
+        return fail(LIO_ERR_ARG, what + ": dilate must be odd and in 1..15");
+    if (const int rc = gaussian_arg(what, p->ksize, sigma)) return rc;
+    lio::gaussian_weights(p->ksize, sigma, p->w);
+    return LIO_OK;
+}
+
+int lio_gaussian_weights(int ksize, double sigma, uint16_t* w) {
+    const char* what = "lio_gaussian_weights";
+    if (!w) return fail(LIO_ERR_ARG, std::string(what) + ": w is NULL");
+    if (const int rc = gaussian_arg(what, ksize, sigma)) return rc;
+    lio::gaussian_weights(ksize, sigma, w);
+    return LIO_OK;
+}
+
+int lio_exposure_gaussian_blur(lio_exposure* h, const uint8_t* image, int width, int height, int channels, int64_t pitch,
+                               int ksize, double sigma, uint8_t* out, int64_t out_pitch) {
+    const char* what = "lio_exposure_gaussian_blur";
+    int rc = exposure_image_arg(what, image, width, height, channels, pitch, 0, out, true, out_pitch);
+    if (rc) return rc;
+    if ((rc = gaussian_arg(what, ksize, sigma))) return rc;
+    uint16_t w[lio::kOxMaxKsize + 1] = {};
+    lio::gaussian_weights(ksize, sigma, w);
+    if ((rc = null_handle(h, what))) return rc;
+    HIP_TRY(hipSetDevice(h->dev));
+    return status(lio::exposure_gaussian_blur(h->e, image, width, height, channels, pitch, ksize, w, out, out_pitch, h->st), what);
+}
+
+int lio_exposure_recover(lio_exposure* h, const uint8_t* image, int width, int height, int channels, int64_t pitch, int order,
+                         const lio_recover_params* p_opt, uint8_t* out, int64_t out_pitch) {
+    const char* what = "lio_exposure_recover";
+    int rc = exposure_image_arg(what, image, width, height, channels, pitch, order, out, true, out_pitch);
+    if (rc) return rc;
+    lio::OxRecover p{};
+    if ((rc = recover_arg(what, p_opt, &p))) return rc;
+    if ((rc = null_handle(h, what))) return rc;
+    HIP_TRY(hipSetDevice(h->dev));
+    return status(lio::exposure_recover(h->e, image, width, height, channels, pitch, order, p, out, out_pitch, h->st), what);
+}
+
+int lio_exposure_recover_undistorted(lio_exposure* h, lio_undistorter* undistorter, const uint8_t* raw_image, int64_t pitch,
+                                     int order, const lio_recover_params* p_opt, uint8_t* out, int64_t out_pitch) {
+    const std::string what = "lio_exposure_recover_undistorted";
+    if (!raw_image) return fail(LIO_ERR_ARG, what + ": raw_image is NULL");
+    if (!out) return fail(LIO_ERR_ARG, what + ": out is NULL");
+    if (order != 0 && order != 1) return fail(LIO_ERR_ARG, what + ": order must be 0 (B G R) or 1 (R G B)");
+    lio::OxRecover p{};
+    int rc = recover_arg(what, p_opt, &p);
+    if (rc) return rc;
+    if ((rc = null_handle(h, what.c_str()))) return rc;
+    if (!undistorter) return fail(LIO_ERR_ARG, what + ": undistorter is NULL");
+    if (undistorter->dev != h->dev) return fail(LIO_ERR_ARG, what + ": both handles must be on one device");
+    if ((rc = undistorter_frame_arg(what, undistorter->u, pitch, out_pitch))) return rc;
+    HIP_TRY(hipSetDevice(h->dev));
+    // as in lio_exposure_clahe_undistorted: the undistorter's buffers are used on h's stream
+    return status(lio::exposure_recover_undistorted(h->e, undistorter->u, raw_image, pitch, order, p, out, out_pitch, h->st),
+                  what.c_str());
+}
+
+int lio_exposure_get_stencil_timing(lio_exposure* h, double* ms3) {
+    if (!ms3) return fail(LIO_ERR_ARG, "lio_exposure_get_stencil_timing: ms3 is NULL");
+    const int rc = null_handle(h, "lio_exposure_get_stencil_timing");
+    if (rc) return rc;
+    return stage_times(h->e.stencil_timer, ms3);
 }
 
 }  // extern "C"

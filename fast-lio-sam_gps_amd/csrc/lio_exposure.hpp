@@ -15,6 +15,8 @@ constexpr int kExMaxTiles = 64;         // tiles per direction
 
 // stages of a run, for ExposureBuf::timer (event times of the last run)
 enum ExStage { kExUpload = 0, kExHist = 1, kExLut = 2, kExApply = 3, kExDownload = 4, kExStages = 5 };
+// stages of a stencil run (lio_overexposure.hpp), for ExposureBuf::stencil_timer
+enum OxStage { kOxUpload = 0, kOxKernel = 1, kOxDownload = 2, kOxStages = 3 };
 
 // the tiling of a plane: the extended size, the tile size and the clip value of the contract.  exposure_tiling
 // needs no device; kArg with `why` naming the bound.
@@ -35,6 +37,7 @@ struct ExposureBuf {
     uint32_t* h_small = nullptr;  // pinned, 2 x 256 uint32: the histograms down, the two tables up
     size_t h_small_bytes = 0;
     StageTimer<kExStages> timer;
+    StageTimer<kOxStages> stencil_timer;  // of the stencil calls (lio_overexposure.hpp), which use in and out alone
 };
 int exposure_init(ExposureBuf& e);
 void exposure_free(ExposureBuf& e);

@@ -63,6 +63,8 @@ EXPORTS = [
     "lio_undistorter_run", "lio_undistorter_get_timing",
     "lio_exposure_create", "lio_exposure_destroy", "lio_exposure_histograms", "lio_exposure_clahe", "lio_exposure_remap",
     "lio_exposure_clahe_undistorted", "lio_exposure_get_timing",
+    "lio_gaussian_weights", "lio_exposure_gaussian_blur", "lio_exposure_recover", "lio_exposure_recover_undistorted",
+    "lio_exposure_get_stencil_timing",
 ]
 
 
@@ -159,6 +161,10 @@ class Camera(C.Structure):
 class ColorizeParams(C.Structure):
     _fields_ = [("occlusion", C.c_int32), ("splat_radius", C.c_int32), ("depth_rel", C.c_float),
                 ("depth_abs", C.c_float), ("bgr", C.c_int32)]
+
+
+class RecoverParams(C.Structure):  # lio_recover_params
+    _fields_ = [("threshold", C.c_int), ("dilate", C.c_int), ("ksize", C.c_int), ("sigma", C.c_double)]
 
 
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.POINTER(C.c_double), C.c_int64, C.POINTER(C.c_double), C.c_void_p)
@@ -279,6 +285,13 @@ def _declare(L):
         "lio_exposure_clahe_undistorted": (C.c_int, [vp, vp, vp, C.c_int64, C.c_int, C.c_double, C.c_int, C.c_int, vp,
                                                      C.c_int64]),
         "lio_exposure_get_timing": (C.c_int, [vp, dp]),
+        "lio_gaussian_weights": (C.c_int, [C.c_int, C.c_double, C.POINTER(C.c_uint16)]),
+        "lio_exposure_gaussian_blur": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_double, vp,
+                                                 C.c_int64]),
+        "lio_exposure_recover": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.POINTER(RecoverParams), vp,
+                                           C.c_int64]),
+        "lio_exposure_recover_undistorted": (C.c_int, [vp, vp, vp, C.c_int64, C.c_int, C.POINTER(RecoverParams), vp, C.c_int64]),
+        "lio_exposure_get_stencil_timing": (C.c_int, [vp, dp]),
         "lio_ctx_create": (C.c_int, [vp, C.POINTER(MatchParams), C.POINTER(vp)]),
         "lio_ctx_destroy": (C.c_int, [vp]),
         "lio_scan_set": (C.c_int, [vp, fp, C.c_int64]),

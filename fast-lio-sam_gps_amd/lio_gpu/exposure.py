@@ -1,7 +1,9 @@
 """Exposure adaption of camera frames: the step the reference runs on every rectified image
 (post_process/exposure_adaption), over the C-ABI.
 
-* :class:`Exposure` — ``histograms``, ``clahe``, ``remap``, ``clahe_undistorted`` (``lio_exposure_*``)
+* :class:`Exposure` — ``histograms``, ``clahe``, ``remap``, ``clahe_undistorted`` (``lio_exposure_*``), and the stencil
+  calls ``recover`` (``solve_overexposure``'s ``recover_overexposure``), ``gaussian_blur``, ``recover_undistorted``
+* :func:`gaussian_weights` — the fixed-point weights of the 8-bit Gaussian blur
 * :func:`equalize_lut`, :func:`stretch_lut`, :func:`gamma_lut`, :func:`detect_exposure` — the host side of
   ``correct_exposure``: 256-entry tables from a 256-bin histogram, a few hundred operations per frame
 * :func:`adapt_exposure` — ``CLAHE_region_adjusted.py``'s function (clip 2.0, 8 x 8 tiles);
@@ -17,7 +19,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._capi import check, lib
+from ._capi import RecoverParams, check, lib
 from .camera import _out, _plane
 from .filters import _Handle
 
@@ -102,6 +104,14 @@ def detect_exposure(hist_gray) -> str:
     return "well-exposed"
 
 
+def gaussian_weights(ksize: int, sigma: float = 0.0) -> np.ndarray:
+    """the ``ksize`` fixed-point weights (uint16, 8 fractional bits, their sum is 256) of the 8-bit Gaussian blur, from
+    the library (``lio_gaussian_weights``; host only, no device is needed)"""
+    w = np.zeros(max(int(ksize), 1), np.uint16)
+    check(lib().lio_gaussian_weights(int(ksize), float(sigma), w.ctypes.data_as(C.POINTER(C.c_uint16))))
+    return w
+
+
 # ------------------------------------------------------------------------------------------------- the handle
 def _table(lut, name):
     if lut is None:
@@ -178,6 +188,50 @@ class Exposure(_Handle):
     def timing(self) -> dict:
         """device ms of the last run: upload (staging copy included), histogram, LUT, apply, download"""
         return self._timing("lio_exposure_get_timing", ("upload_ms", "hist_ms", "lut_ms", "apply_ms", "download_ms"))
+
+    def recover(self, image, threshold: int = 200, dilate: int = 5, ksize: int = 15, sigma: float = 0.0, order: int = BGR,
+                out=None) -> np.ndarray:
+        """``solve_overexposure``'s ``recover_overexposure``: where the mask ``V > threshold``, dilated by ``dilate x
+        dilate``, is set, V becomes its ``ksize x ksize`` Gaussian blur; H and S are kept (on a plane: the plane)"""
+        img, pitch, ch = self._image(image)
+        h, w = img.shape[:2]
+        out, o = _out(out, np.shape(image), ch, w)
+        p = RecoverParams(int(threshold), int(dilate), int(ksize), float(sigma))
+        check(lib().lio_exposure_recover(self._h, img.ctypes.data_as(C.c_void_p), w, h, ch, pitch, int(order), C.byref(p),
+                                         o.ctypes.data_as(C.c_void_p), o.strides[0]))
+        return out
+
+    def gaussian_blur(self, image, ksize: int, sigma: float = 0.0, out=None) -> np.ndarray:
+        """``cv2.GaussianBlur(image, (ksize, ksize), sigma)`` of a uint8 image, every channel"""
+        img, pitch, ch = self._image(image)
+        h, w = img.shape[:2]
+        out, o = _out(out, np.shape(image), ch, w)
+        check(lib().lio_exposure_gaussian_blur(self._h, img.ctypes.data_as(C.c_void_p), w, h, ch, pitch, int(ksize), float(sigma),
+                                               o.ctypes.data_as(C.c_void_p), o.strides[0]))
+        return out
+
+    def recover_undistorted(self, undistorter, raw, threshold: int = 200, dilate: int = 5, ksize: int = 15, sigma: float = 0.0,
+                            order: int = BGR, out=None) -> np.ndarray:
+        """``undistorter(raw)`` followed by :meth:`recover`, bit for bit, with one upload and one download"""
+        p = RecoverParams(int(threshold), int(dilate), int(ksize), float(sigma))
+        if undistorter._shape is None:  # the library's state error, with its message
+            z = np.zeros(1, np.uint8)
+            check(lib().lio_exposure_recover_undistorted(self._h, undistorter._h, z.ctypes.data_as(C.c_void_p), 0, int(order),
+                                                         C.byref(p), z.ctypes.data_as(C.c_void_p), 0))
+        sh, sw, dh, dw, ch = undistorter._shape
+        img, pitch, c = _plane(raw, sw, sh)
+        if c != ch:
+            raise ValueError(f"raw: {c} channel(s), the undistorter was set up for {ch}")
+        shape = (dh, dw) if np.ndim(raw) == 2 else (dh, dw, ch)
+        out, o = _out(out, shape, ch, dw)
+        check(lib().lio_exposure_recover_undistorted(self._h, undistorter._h, img.ctypes.data_as(C.c_void_p), pitch, int(order),
+                                                     C.byref(p), o.ctypes.data_as(C.c_void_p), o.strides[0]))
+        return out
+
+    def stencil_timing(self) -> dict:
+        """device ms of the last ``recover``, ``gaussian_blur`` or ``recover_undistorted``: upload (staging copy
+        included; chained: the undistorter's upload and gather), the kernel, download"""
+        return self._timing("lio_exposure_get_stencil_timing", ("upload_ms", "kernel_ms", "download_ms"))
 
 
 # ------------------------------------------------------------------------------------------ the scripts' functions

@@ -986,6 +986,69 @@ int lio_exposure_clahe_undistorted(lio_exposure* h, lio_undistorter* undistorter
                                    int order, double clip_limit, int tiles_x, int tiles_y, uint8_t* out, int64_t out_pitch);
 int lio_exposure_get_timing(lio_exposure* h, double* ms5);
 
+/* ------------------------------ overexposure recovery and the 8-bit Gaussian blur (stencils on a lio_exposure) */
+/* The third script of post_process/exposure_adaption: solve_overexposure:6-32 (recover_overexposure: BGR -> HSV, a
+ * mask V > 200, cv2.dilate of it with a 5 x 5 block of ones, cv2.GaussianBlur(v, (15, 15), 0), np.where(mask > 0,
+ * blurred_v, v), the new V merged with the old H and S, HSV -> BGR), and cv2.GaussianBlur of an 8-bit image as a call
+ * of its own.  The contract is the library's own, integer-only on the device and exact to the bit; it is our reading
+ * of OpenCV 4's 8-bit paths (ufixedpoint16 rows, ufixedpoint32 columns).  AGREEMENT WITH cv2 IS OUR READING OF ITS
+ * SOURCE AND IS UNVERIFIED: OpenCV was not available where this was written.
+ *   images, order, pitches   exactly those of lio_exposure_* above: uint8, channels 1 or 3, width and height in
+ *            1..32767, only channels x width bytes of a row read or written.
+ *   V        max(b, g, r); with 1 channel the pixel itself.
+ *   mask     m0(x, y) = V(x, y) > threshold, STRICT, threshold in 0..255 (script: 200).  rd = (dilate - 1) / 2, dilate
+ *            ODD in 1..15 (script: 5).  M(x, y) = OR of m0 over |dx| <= rd, |dy| <= rd, taken ONLY OVER POSITIONS
+ *            INSIDE THE IMAGE (cv2.dilate's default constant border, which never wins a maximum).
+ *   weights  lio_gaussian_weights: k = ksize uint16 values with 8 fractional bits that SUM TO 256, computed on the host;
+ *            ksize ODD in 1..31 (script: 15), sigma a double (script: 0), NaN or +-inf is LIO_ERR_ARG.
+ *            If sigma <= 0 and k <= 7, g is OpenCV's fixed table: {1}, {.25, .5, .25}, {.0625, .25, .375, .25, .0625},
+ *            {.03125, .109375, .21875, .28125, .21875, .109375, .03125}.  Otherwise, all in double:
+ *            s = sigma > 0 ? sigma : ((k - 1) 0.5 - 1) 0.3 + 0.8; x = i - (k - 1) 0.5;
+ *            t[i] = exp(((-0.5 / (s s)) x) x); g[i] = t[i] (1 / sum t), the sum taken from i = 0 up.
+ *            Fixed point with error diffusion over the left half, err = 0 at the start; for i = 0 .. k / 2 - 1:
+ *            a = g[i] 256 + err; w[i] = w[k - 1 - i] = rint(a), TIES TO EVEN; err = a - w[i].
+ *            Then w[k / 2] = 256 - 2 sum w[i].  k = 15, sigma = 0 gives 1 3 6 12 20 30 36 40 36 30 20 12 6 3 1.
+ *            The device only ever sees these integers.
+ *   blur     r = k / 2.  Hrow(x, y) = sum_j w[j] V(refl(x + j - r, W), y), at most 65 280: it fits 16 bits.
+ *            B(x, y) = (sum_j w[j] Hrow(x, refl(y + j - r, H)) + 32768) >> 16.
+ *            refl is REFLECT_101 APPLIED UNTIL THE INDEX IS IN RANGE: n == 1: 0; otherwise q = p mod 2 (n - 1)
+ *            (non-negative) and refl = q < n ? q : 2 (n - 1) - q.  An image narrower than the radius is legal.
+ *   blend    V' = M ? B : V.
+ *   output   3 channels: (h, s) from the BGR -> HSV above of the pixel, then the HSV -> BGR above of (h, s, V') ON
+ *            EVERY PIXEL, MASKED OR NOT (the script round-trips the whole frame, and the round trip is lossy).
+ *            1 channel: V'.
+ *
+ * lio_gaussian_weights: ksize values to w.  Host only: it needs no device and no handle.
+ * lio_exposure_gaussian_blur: the blur above on each channel of a 1- or 3-channel image, as cv2.GaussianBlur(img,
+ *   (k, k), sigma): a square kernel, one sigma for both axes.  ksize 1 is the identity.
+ * lio_exposure_recover: the recovery.  p_opt NULL means the script's {200, 5, 15, 0}.
+ * lio_exposure_recover_undistorted: the undistorter's configured frame is rectified and recovered with ONE UPLOAD AND
+ *   ONE DOWNLOAD; the result equals lio_undistorter_run followed by lio_exposure_recover bit for bit.  The device and
+ *   state rules are those of lio_exposure_clahe_undistorted.
+ * lio_exposure_get_stencil_timing: device ms of the last of the three calls above from stream events: upload (its
+ *   staging copy included; in the chained call the undistorter's upload and gather), the kernel, download.
+ *   lio_exposure_get_timing and its five stages are those of the earlier calls alone.
+ * LIO_ERR_ARG before any device work, with a message that names the bound: the image bounds of lio_exposure_*, a NULL
+ * image, out, raw_image, w or ms3, a threshold outside 0..255, a dilate even or outside 1..15, a ksize even or outside
+ * 1..31, a sigma that is not finite, pitch or out_pitch < channels x width.  The checks that need no handle are made
+ * before the handle is looked at.  There is no CPU path: LIO_ERR_NODEV without a device.  From the second frame of
+ * one size on nothing is allocated (lio_alloc_count); repeated runs give identical bits.                          */
+struct lio_recover_params {
+    int threshold; /* 0..255; the script: 200 */
+    int dilate;    /* odd, 1..15; the script: 5 */
+    int ksize;     /* odd, 1..31; the script: 15 */
+    double sigma;  /* <= 0: from ksize; the script: 0 */
+};
+typedef struct lio_recover_params lio_recover_params;
+int lio_gaussian_weights(int ksize, double sigma, uint16_t* w);
+int lio_exposure_gaussian_blur(lio_exposure* h, const uint8_t* image, int width, int height, int channels, int64_t pitch,
+                               int ksize, double sigma, uint8_t* out, int64_t out_pitch);
+int lio_exposure_recover(lio_exposure* h, const uint8_t* image, int width, int height, int channels, int64_t pitch, int order,
+                         const lio_recover_params* p_opt, uint8_t* out, int64_t out_pitch);
+int lio_exposure_recover_undistorted(lio_exposure* h, lio_undistorter* undistorter, const uint8_t* raw_image, int64_t pitch,
+                                     int order, const lio_recover_params* p_opt, uint8_t* out, int64_t out_pitch);
+int lio_exposure_get_stencil_timing(lio_exposure* h, double* ms3);
+
 #ifdef __cplusplus
 }
 #endif

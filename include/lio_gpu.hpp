@@ -1036,6 +1036,22 @@ inline int detect_exposure(const ExposureHist& hist_gray) {
     return 0;
 }
 
+// The parameters of Exposure::recover; the defaults are solve_overexposure's (lio_recover_params).
+struct RecoverParams {
+    int threshold = 200;
+    int dilate = 5;
+    int ksize = 15;
+    double sigma = 0.0;
+    lio_recover_params c() const { return lio_recover_params{threshold, dilate, ksize, sigma}; }
+};
+
+// The ksize fixed-point weights of the 8-bit Gaussian blur (8 fractional bits, their sum is 256).  Needs no device.
+inline std::vector<uint16_t> gaussian_weights(int ksize, double sigma = 0.0) {
+    std::vector<uint16_t> w(ksize > 0 ? (size_t)ksize : 0);
+    check(lio_gaussian_weights(ksize, sigma, w.data()), "gaussian_weights");
+    return w;
+}
+
 // Exposure adaption of frames (lio_exposure): histograms, CLAHE of V (CLAHE_region_adjusted.py's adapt_exposure with the
 // defaults), table remaps, and the undistorter's frame adapted on the device.  Images: rows of `pitch` bytes (0:
 // channels * width); order 0 = B G R, 1 = R G B.
@@ -1077,6 +1093,35 @@ public:
     std::array<double, 5> timing() {
         std::array<double, 5> ms{};
         check(lio_exposure_get_timing(h_, ms.data()), "Exposure::timing");
+        return ms;
+    }
+    // solve_overexposure's recover_overexposure: V blurred where the dilated mask V > threshold is set
+    void recover(const uint8_t* image, int width, int height, int channels, uint8_t* out, const RecoverParams& p = RecoverParams(),
+                 int order = 0, int64_t pitch = 0, int64_t out_pitch = 0) {
+        const lio_recover_params c = p.c();
+        check(lio_exposure_recover(h_, image, width, height, channels, pitch ? pitch : (int64_t)channels * width, order, &c, out,
+                                   out_pitch ? out_pitch : (int64_t)channels * width),
+              "Exposure::recover");
+    }
+    // cv2.GaussianBlur(img, (ksize, ksize), sigma) of an 8-bit image, every channel
+    void gaussian_blur(const uint8_t* image, int width, int height, int channels, uint8_t* out, int ksize, double sigma = 0.0,
+                       int64_t pitch = 0, int64_t out_pitch = 0) {
+        check(lio_exposure_gaussian_blur(h_, image, width, height, channels, pitch ? pitch : (int64_t)channels * width, ksize, sigma,
+                                         out, out_pitch ? out_pitch : (int64_t)channels * width),
+              "Exposure::gaussian_blur");
+    }
+    // ud.undistort(raw) then recover, bit for bit, with one upload and one download
+    void recover_undistorted(Undistorter& ud, const uint8_t* raw, uint8_t* out, const RecoverParams& p = RecoverParams(),
+                             int order = 0, int64_t pitch = 0, int64_t out_pitch = 0) {
+        const lio_recover_params c = p.c();
+        check(lio_exposure_recover_undistorted(h_, ud.handle(), raw, pitch ? pitch : (int64_t)ud.channels() * ud.rawWidth(), order,
+                                               &c, out, out_pitch ? out_pitch : (int64_t)ud.channels() * ud.width()),
+              "Exposure::recover_undistorted");
+    }
+    // device ms of the last recover, gaussian_blur or recover_undistorted: upload, kernel, download
+    std::array<double, 3> stencil_timing() {
+        std::array<double, 3> ms{};
+        check(lio_exposure_get_stencil_timing(h_, ms.data()), "Exposure::stencil_timing");
         return ms;
     }
 
