@@ -1,6 +1,6 @@
 // lio_capi_post.cpp — the C-ABI (include/lio_gpu.h) of the offline leg's point cloud steps on a lio_filter:
 // statistical outlier removal and the intensity map denoise, Euclidean clusters and DBSCAN, GPS-to-SLAM
-// alignment and georeferencing, RANSAC plane segmentation.  The handle's create / destroy are in lio_capi.cpp.
+// alignment and georeferencing, RANSAC plane segmentation, k-means.  The handle's create / destroy are in lio_capi.cpp.
 #include <algorithm>
 
 #include "lio_capi_util.hpp"
@@ -274,6 +274,46 @@ int lio_segment_plane(lio_filter* f, const float* pts, int64_t n, int stride, fl
     *best_iteration = pr.best;
     *n_inliers = pr.n_inliers;
     if (refit4_opt) std::memcpy(refit4_opt, pr.refit, sizeof(pr.refit));
+    return LIO_OK;
+}
+
+// ---- k-means with k-means++ seeding and per-cluster boxes (lio_kmeans.hip) ----
+// The arguments are judged before the handle, so a bad call is LIO_ERR_ARG with or without a device.
+int lio_kmeans(lio_filter* f, const float* pts, int64_t n, int stride, int K, int max_iter, float eps, int attempts,
+               uint64_t seed, const float* init_centers_opt, int32_t* labels_out, float* centers_out,
+               double* compactness_out, int64_t* counts_opt, float* aabb6_opt, int32_t* seeds_opt,
+               uint64_t* attempt_q_opt, int32_t* attempt_iters_opt, int64_t* stats6_opt) {
+    if (!centers_out || !compactness_out || n < 0 || n >= (int64_t)1 << 31 || (n > 0 && (!pts || !labels_out)) ||
+        stride < 3 || stride > lio::kMaxFields || K < 1 || K > lio::kKmMaxK || attempts < 1 ||
+        attempts > lio::kKmMaxAttempts || max_iter < 1 || max_iter > lio::kKmMaxIter || !(eps >= 0.f) || !std::isfinite(eps))
+        return fail(LIO_ERR_ARG, "lio_kmeans: bad arguments");
+    if (init_centers_opt)
+        for (int64_t k = 0; k < (int64_t)attempts * K * 3; ++k)
+            if (!std::isfinite(init_centers_opt[k]))
+                return fail(LIO_ERR_ARG, "lio_kmeans: an initial centre is not finite");
+    if (n < K) return fail(LIO_ERR_ARG, "lio_kmeans: fewer finite points than clusters");
+    int rc = null_handle(f, "lio_kmeans");
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(f->dev));
+    if ((rc = upload_in(f, pts, n * stride))) return rc;
+    lio::KMeansArgs ka;
+    ka.K = K, ka.max_iter = max_iter, ka.attempts = attempts, ka.eps = eps, ka.seed = seed, ka.init_centers = init_centers_opt;
+    lio::KMeansResult kr;
+    rc = lio::kmeans(f->km, f->d_in, pts, n, stride, ka, aabb6_opt != nullptr, &kr, f->st);
+    if (rc) return status(rc, "lio_kmeans", lio::last_error().c_str());
+    HIP_TRY(hipMemcpyAsync(labels_out, kr.labels, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, f->st));
+    HIP_TRY(hipStreamSynchronize(f->st));
+    std::memcpy(centers_out, kr.centers, (size_t)K * 3 * sizeof(float));
+    *compactness_out = std::ldexp((double)kr.attempt_q[kr.best], kr.ed - 31);
+    if (counts_opt) std::memcpy(counts_opt, kr.counts, (size_t)K * sizeof(int64_t));
+    if (aabb6_opt) std::memcpy(aabb6_opt, kr.aabb, (size_t)K * 6 * sizeof(float));
+    if (seeds_opt) std::memcpy(seeds_opt, kr.seeds, (size_t)attempts * K * sizeof(int32_t));
+    if (attempt_q_opt) std::memcpy(attempt_q_opt, kr.attempt_q, (size_t)attempts * sizeof(uint64_t));
+    if (attempt_iters_opt) std::memcpy(attempt_iters_opt, kr.attempt_iters, (size_t)attempts * sizeof(int32_t));
+    if (stats6_opt) {
+        const int64_t s6[6] = {kr.nf, kr.best, kr.attempt_iters[kr.best], kr.repairs, kr.ec, kr.ed};
+        std::memcpy(stats6_opt, s6, sizeof(s6));
+    }
     return LIO_OK;
 }
 

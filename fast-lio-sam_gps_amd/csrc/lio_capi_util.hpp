@@ -15,6 +15,7 @@
 #include "lio_kernels.hpp"  // PoseArg, which lio_filter.hpp uses
 #include "lio_filter.hpp"
 #include "lio_gpsalign.hpp"
+#include "lio_kmeans.hpp"
 #include "lio_plane.hpp"
 #include "lio_scratch.hpp"
 
@@ -109,6 +110,7 @@ struct lio_filter : lio::capi::Handle {
     lio::DenoiseBuf dn;  // lio_sor_filter / lio_radius_first_seed / lio_denoise_slam_map
     lio::ClusterBuf cl;  // lio_euclidean_clusters, lio_dbscan (with dn: the grid, the sorts and the scan)
     lio::PlaneBuf pl;    // lio_segment_plane (with dn: the flags and the scan)
+    lio::KMeansBuf km;   // lio_kmeans
     lio::GpsAlignBuf ga; // lio_gps_align, lio_similarity2d_fit, lio_georeference_xy
     lio::ProjectBuf pj;  // lio_project_points, lio_undistort_map
 };

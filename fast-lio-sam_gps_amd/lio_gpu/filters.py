@@ -14,6 +14,8 @@
   box per cluster (fast_lio_sam.cpp:343-363, post_process/clustering.py:39-75)
 * :class:`DBSCAN` — the offline pipeline's other clustering method (post_process/clustering.py:30-36), with
   core flags and one box per cluster
+* :class:`KMeans`, :func:`cluster_palette` — the projection tool's ``cv::kmeans`` call and its cluster colours
+  (post_process/lidar_projection/src/lidar_projection.cpp:82-92, 36-52)
 
 Point records are float rows ``[x, y, z, attr...]`` (3..8 floats); PCL's
 PointXYZI is ``stride = 4``, FAST-LIO's PointXYZINormal-with-time is
@@ -306,6 +308,83 @@ class PlaneSegmentation(_Handle):
         self.best_iteration = best.value
         self.counts, self.sq, self.degenerate, self.mask, self.refit = counts, sq, degenerate, mask, refit
         return plane, inliers[: m.value].copy()
+
+
+class KMeans(_Handle):
+    """``cv::kmeans`` as the reference's projection tool calls it (post_process/lidar_projection/src/
+    lidar_projection.cpp:82-92: 5 clusters, ``TermCriteria(EPS + MAX_ITER, 100, 0.1)``, 3 attempts, k-means++
+    centres), by the contract of ``lio_kmeans``: k-means++ seeding with three trials per centre from a
+    counter-based sampler, Lloyd iterations on fixed-point sums (so no result depends on the device's schedule),
+    empty clusters repaired from the largest one, the attempt with the smallest compactness kept.  It follows
+    OpenCV's procedure; it is not bit parity with it.  Centres are float32: subtract an origin from map coordinates
+    first (:func:`lio_gpu.georef.georeference_xy` offers one).
+    After :meth:`fit`: ``labels_`` (-1 for a non-finite point), ``cluster_centers_``, ``inertia_`` (the
+    compactness; scikit-learn's names), ``n_iter_``, ``best_attempt``, ``counts``, ``aabb`` (per cluster min x, y,
+    z, max x, y, z), ``seeds`` (attempts x K point indices, -1 with ``init_centers``), ``attempt_q`` /
+    ``attempt_iters`` (per attempt) and ``stats`` = finite points, best attempt, its iterations, repairs, ec, ed."""
+
+    def __init__(self, n_clusters: int = 5, max_iter: int = 100, eps: float = 0.1, attempts: int = 3, seed: int = 0,
+                 device: int = 0):
+        super().__init__(device)
+        self.n_clusters = int(n_clusters)
+        self.max_iter = int(max_iter)
+        self.eps = float(eps)
+        self.attempts = int(attempts)
+        self.seed = int(seed)
+        self.labels_ = np.zeros(0, np.int32)
+        self.cluster_centers_ = np.zeros((0, 3), np.float32)
+        self.inertia_ = 0.0
+        self.n_iter_ = 0
+        self.best_attempt = 0
+        self.counts = np.zeros(0, np.int64)
+        self.aabb = np.zeros((0, 6), np.float32)
+        self.seeds = np.zeros((0, 0), np.int32)
+        self.attempt_q = np.zeros(0, np.uint64)
+        self.attempt_iters = np.zeros(0, np.int32)
+        self.stats = np.zeros(6, np.int64)
+
+    def fit(self, pts: np.ndarray, init_centers=None) -> np.ndarray:
+        """The labels.  ``init_centers`` (attempts x K x 3) replaces the seeding of every attempt."""
+        pts2 = _rows(pts)
+        n, k, a = len(pts2), max(self.n_clusters, 0), max(self.attempts, 0)
+        init = None
+        if init_centers is not None:
+            init = np.ascontiguousarray(init_centers, dtype=np.float32)
+            if init.shape != (a, k, 3):
+                raise ValueError("init_centers must be attempts x n_clusters x 3")
+        labels = np.full(n, -1, np.int32)
+        centers = np.zeros((k, 3), np.float32)
+        counts, aabb = np.zeros(k, np.int64), np.zeros((k, 6), np.float32)
+        seeds = np.full((a, k), -1, np.int32)
+        attempt_q, attempt_iters = np.zeros(a, np.uint64), np.zeros(a, np.int32)
+        stats = np.zeros(6, np.int64)
+        compactness = C.c_double(0.0)
+        i32p, i64p = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+        check(lib().lio_kmeans(self._h, _fp(pts2), n, pts2.shape[1], self.n_clusters, self.max_iter, self.eps,
+                               self.attempts, self.seed & (2**64 - 1), _fp(init) if init is not None else None,
+                               labels.ctypes.data_as(i32p), _fp(centers), C.byref(compactness),
+                               counts.ctypes.data_as(i64p), _fp(aabb), seeds.ctypes.data_as(i32p),
+                               attempt_q.ctypes.data_as(C.POINTER(C.c_uint64)), attempt_iters.ctypes.data_as(i32p),
+                               stats.ctypes.data_as(i64p)))
+        self.labels_, self.cluster_centers_, self.inertia_ = labels, centers, compactness.value
+        self.counts, self.aabb, self.seeds = counts, aabb, seeds
+        self.attempt_q, self.attempt_iters, self.stats = attempt_q, attempt_iters, stats
+        self.best_attempt, self.n_iter_ = int(stats[1]), int(stats[2])
+        return labels
+
+
+# the ten B, G, R colours of the projection tool's overlay (lidar_projection.cpp:38-49)
+CLUSTER_PALETTE_BGR = np.array([(255, 0, 0), (0, 255, 0), (0, 0, 255), (255, 255, 0), (255, 0, 255), (0, 255, 255),
+                                (128, 0, 0), (0, 128, 0), (0, 0, 128), (128, 128, 0)], np.uint8)
+
+
+def cluster_palette(labels) -> np.ndarray:
+    """n x 3 uint8 B, G, R: the projection tool's colour of each point's cluster (``label % 10``), black for -1.
+    Host only; the drawing itself is the caller's."""
+    lab = np.asarray(labels).astype(np.int64).reshape(-1)
+    out = CLUSTER_PALETTE_BGR[np.mod(lab, 10)]
+    out[lab < 0] = 0
+    return out
 
 
 def cluster_objects(pts, nb_neighbors=20, std_ratio=2.0, distance_threshold=0.2, num_iterations=1000, seed=0,

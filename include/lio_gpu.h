@@ -628,6 +628,56 @@ int lio_segment_plane(lio_filter* f, const float* pts, int64_t n, int stride, fl
  * n >= 2^31, num_iterations < 0 or > 2^20, NULL out with something to write.                                   */
 int lio_plane_sample_triples(uint64_t seed, int64_t n, int64_t num_iterations, int32_t* out);
 
+/* k-means with k-means++ seeding and one bounding box per cluster: the cv::kmeans call of the reference's
+ * projection tool (post_process/lidar_projection/src/lidar_projection.cpp:82-92: K 5, TermCriteria(EPS +
+ * MAX_ITER, 100, 0.1), 3 attempts, KMEANS_PP_CENTERS), OpenCV's procedure [U] followed step by step and restated
+ * as a contract of this library; it is not bit parity with cv::kmeans or cv::RNG.  pts is n x stride floats (x,
+ * y, z first; stride 3..8), 0 <= n < 2^31; 1 <= K <= 64, 1 <= attempts <= 16, 1 <= max_iter <= 1000, eps finite
+ * and >= 0.  All float arithmetic is in the written order without contraction, as everywhere in the library.
+ *   points    a point with a non-finite x, y or z takes no part: label -1, in no sum.  nf = the finite points.
+ *             nf < K is LIO_ERR_ARG (OpenCV asserts N >= K [U]): before any device work when n < K (n = 0 included:
+ *             K >= 1 > nf), else after the counting pass; nothing is written.
+ *   scales    from the finite points' box (lo, hi per axis).  Coordinates: A = the largest of |lo|, |hi| over the
+ *             axes, (m, ec) = frexp(A) (ec = 0 when A = 0), qx_i = (int64) rint((double) x_i 2^(31 - ec)): exact in
+ *             double, |qx_i| <= 2^31.  Distances: ex = hi_x - lo_x (float; ey, ez alike), D2 = (ex ex + ey ey) +
+ *             ez ez (float; must be finite, else LIO_ERR_ARG), (m, ed) = frexp(D2) (ed = 0 when D2 = 0),
+ *             q(d) = (uint64) floor((double) d 2^(31 - ed)) < 2^32 for every squared distance d inside the box.
+ *             d2(p, c) = (dx dx + dy dy) + dz dz in float with dx = p_x - c_x.  Every sum below is an integer sum.
+ *   draws     mod 2^64: r(c) = mix(seed + (c + 1) 0x9E3779B97F4A7C15), mix as in lio_plane_sample_triples;
+ *             attempt a, centre k, trial j uses c = (a K + k) 3 + j (centre 0: j = 0).
+ *   seeding   per attempt, unless init_centers_opt (attempts x K x 3 finite floats) replaces it: OpenCV's
+ *             generateCentersPP with 3 trials [U].  Centre 0 is the (r(c) mod nf)-th finite point in index
+ *             order; w_i = q(d2(p_i, centre 0)), 0 for a non-finite point.  For k = 1 .. K - 1: sum0 = sum w_i;
+ *             trial j: u = r(c) >> 11, t = (u sum0) >> 53 (128-bit product), the candidate ci is the lowest
+ *             index whose inclusive prefix sum of w exceeds t (the lowest finite index when sum0 = 0),
+ *             w'_i = min(q(d2(p_i, p_ci)), w_i), s = sum w'_i; the trial with the smallest s wins, THE LOWEST j
+ *             AMONG EQUALS; its ci is centre k and w becomes its w'.
+ *   Lloyd     [U] assign every finite point to the centre with the smallest d2 (strict < over ascending k: THE
+ *             LOWEST k WINS A TIE), it = 1.  Then repeat: per cluster cnt_k and S_k = sum (qx, qy, qz); for k
+ *             ascending with cnt_k = 0 the repair: mk = the cluster with the largest count (lowest index among
+ *             equals), its member with the largest float d2 to mk's current mean (THE LOWEST INDEX AMONG EQUALS:
+ *             this library's tie-break) moves to k (label, both counts, both sums); c_k = (float)(((double) S_k
+ *             / (double) cnt_k) 2^(ec - 31)) per axis; shift = max over k of (tx tx + ty ty) + tz tz in double,
+ *             tx = the float c_new,x - c_old,x widened; it += 1; stop when it == max(max_iter, 2) or
+ *             shift <= (double) eps * eps, else assign again.  AT THE STOP THE LABELS ARE NOT REASSIGNED: every
+ *             centre is exactly the mean of its members.  cq = sum q(d2(p_i, c_label_i)) over the finite points.
+ *   result    the attempt with the smallest cq, the lowest attempt among equals.
+ * labels_out (n); centers_out (K x 3); *compactness_out = (double) cq 2^(ed - 31).  May be NULL, each of them:
+ * counts_opt (K); aabb6_opt (K x 6: float min x, y, z, max x, y, z over each cluster's members); seeds_opt
+ * (attempts x K: the chosen point indices, -1 everywhere with init_centers_opt); attempt_q_opt / attempt_iters_opt
+ * (per attempt cq and it); stats6_opt = nf, best attempt, its it, repairs over all attempts, ec, ed.
+ * Centres are float32, as OpenCV's: at map coordinates of 8e5 m a float ulp is 6 cm, so subtract an origin
+ * first (lio_georeference_xy offers one).
+ * LIO_ERR_ARG before any device work, with or without a device: every range above, a non-finite
+ * init_centers_opt entry, NULL pts / labels_out with n > 0, NULL centers_out / compactness_out, n < K.
+ * Repeated calls and any scheduling of the device give identical bits; a repeated call of one size allocates
+ * nothing (lio_alloc_count).                                                                                    */
+int lio_kmeans(lio_filter* f, const float* pts, int64_t n, int stride, int K, int max_iter, float eps,
+               int attempts, uint64_t seed, const float* init_centers_opt,
+               int32_t* labels_out, float* centers_out, double* compactness_out,
+               int64_t* counts_opt, float* aabb6_opt, int32_t* seeds_opt,
+               uint64_t* attempt_q_opt, int32_t* attempt_iters_opt, int64_t* stats6_opt);
+
 /* ------------------------------- GPS-to-SLAM trajectory alignment and map georeferencing (offline GPS leg) */
 /* Layout of lio_gps_align's result (doubles).  Pairs are (x, y); a rotation is (c, s) for [[c, -s], [s, c]]. */
 #define LIO_GPSALIGN_ITERATIONS 0  /* iterations run                                                          */

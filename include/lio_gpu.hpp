@@ -1167,6 +1167,65 @@ private:
     double refit_[4] = {0, 0, 0, 0};
 };
 
+// cv::kmeans as the reference's projection tool calls it (post_process/lidar_projection/src/lidar_projection.cpp:
+// 82-92), by the contract of lio_kmeans (lio_gpu.h): k-means++ seeding from a counter-based sampler, Lloyd with
+// fixed-point sums, the best of `attempts` runs.  setInputCloud / setK / setTermCriteria / setAttempts / setSeed /
+// setInitialCenters / compute, which returns the compactness as cv::kmeans does.  The defaults are the reference's
+// call: 5, (100, 0.1), 3 (seed 0).
+template <typename PointT>
+class KMeans {
+public:
+    explicit KMeans(FilterGPU& f) : f_(f) {}
+    void setInputCloud(const std::vector<PointT>* cloud) { in_ = cloud; }
+    void setK(int k) { k_ = k; }
+    void setTermCriteria(int max_iter, double eps) { max_iter_ = max_iter, eps_ = eps; }
+    void setAttempts(int attempts) { attempts_ = attempts; }
+    void setSeed(uint64_t seed) { seed_ = seed; }
+    // attempts x K centres in place of the seeding; an empty vector: seed again
+    void setInitialCenters(const std::vector<std::array<float, 3>>& centers) { init_ = centers; }
+    double compute(std::vector<int>& labels, std::vector<std::array<float, 3>>& centers) {
+        if (!in_) throw Error(LIO_ERR_ARG, "KMeans: no input cloud");
+        const int64_t n = (int64_t)in_->size();
+        const size_t k = (size_t)std::max(k_, 0), a = (size_t)std::max(attempts_, 0);
+        if (!init_.empty() && init_.size() != a * k) throw Error(LIO_ERR_ARG, "KMeans: attempts x K initial centres");
+        static_assert(sizeof(int) == sizeof(int32_t), "labels are int32");
+        labels.assign((size_t)n, -1);
+        centers.assign(k, std::array<float, 3>{});
+        counts_.assign(k, 0);
+        aabbs_.assign(k, ClusterAABB{});
+        seeds_.assign(a * k, -1);
+        double compactness = 0.0;
+        // NULL outputs are an argument error of the library, as is K = 0: hand it a valid address either way
+        float none[3] = {0.f, 0.f, 0.f};
+        check(lio_kmeans(f_.handle(), reinterpret_cast<const float*>(in_->data()), n, float_stride<PointT>(), k_, max_iter_,
+                         (float)eps_, attempts_, seed_, init_.empty() ? nullptr : init_[0].data(), labels.data(),
+                         k ? centers[0].data() : none, &compactness, counts_.data(),
+                         reinterpret_cast<float*>(aabbs_.data()), seeds_.data(), nullptr, nullptr, stats_),
+              "KMeans::compute");
+        return compactness;
+    }
+    // of the last compute(): members and box per cluster; the seeding's point indices (attempts x K, -1 with
+    // initial centres); finite points, best attempt, its iterations, repairs, ec, ed
+    const std::vector<int64_t>& counts() const { return counts_; }
+    const std::vector<ClusterAABB>& aabbs() const { return aabbs_; }
+    const std::vector<int32_t>& seeds() const { return seeds_; }
+    const int64_t* stats() const { return stats_; }
+
+private:
+    FilterGPU& f_;
+    const std::vector<PointT>* in_ = nullptr;
+    int k_ = 5;  // lidar_projection.cpp:82-92
+    int max_iter_ = 100;
+    double eps_ = 0.1;
+    int attempts_ = 3;
+    uint64_t seed_ = 0;
+    std::vector<std::array<float, 3>> init_;
+    std::vector<int64_t> counts_;
+    std::vector<ClusterAABB> aabbs_;
+    std::vector<int32_t> seeds_;
+    int64_t stats_[6] = {0, 0, 0, 0, 0, 0};
+};
+
 struct DenoiseConfig {  // fast_lio_sam.h:123-129, defaults of fast_lio_sam.cpp:89-96 (config.yaml:32-42 sets 0.1, 200, 0.2)
     bool denoise_en = false;
     float seed_thres = 2800.0;
