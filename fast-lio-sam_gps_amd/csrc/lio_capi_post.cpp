@@ -1,6 +1,6 @@
 // lio_capi_post.cpp — the C-ABI (include/lio_gpu.h) of the offline leg's point cloud steps on a lio_filter:
 // statistical outlier removal and the intensity map denoise, Euclidean clusters and DBSCAN, GPS-to-SLAM
-// alignment and georeferencing, RANSAC plane segmentation, k-means.  The handle's create / destroy are in lio_capi.cpp.
+// alignment and georeferencing, RANSAC plane segmentation, k-means.  The handle's create / destroy are in lio_capi_prep.cpp.
 #include <algorithm>
 
 #include "lio_capi_util.hpp"

@@ -1,6 +1,7 @@
 // lio_capi_util.hpp — what every file of the C-ABI (include/lio_gpu.h) shares: the error reporting and the device
 // check (lio_capi_base.hpp), the public code of an internal status, the handle shell, the filter handle and the
-// tails its entry points have in common.  Private to lio_capi.cpp (map, ctx, match, IESKF, filters, preprocessing, formats),
+// tails its entry points have in common.  Private to lio_capi.cpp (the library level), the online leg's files
+// (map, scan context, preprocessing, formats: lio_capi_online.hpp),
 // lio_capi_post.cpp (the offline leg on a lio_filter) and lio_capi_camera.cpp (the camera leg); each says
 // `using namespace lio::capi`.  The functions are static: each file has its own and the library exports none.
 #pragma once
@@ -46,7 +47,7 @@ static inline bool all_finite(const double* v, int64_t count) {
     return true;
 }
 
-// ---- the handle shell: lio_filter, lio_colorizer, lio_undistorter and lio_exposure are a Handle and their buffers ----
+// ---- the handle shell: lio_filter, lio_map, lio_colorizer, lio_undistorter and lio_exposure are a Handle and their buffers ----
 struct Handle {
     int dev = 0;
     hipStream_t st = nullptr;

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "lio_pieces.hpp"
+
 namespace lio {
 
 constexpr int kMaxFields = 8;  // floats per point record (x, y, z, + up to 5 attributes)
@@ -38,8 +40,7 @@ struct UndistortEnd {
 // Where the host packed the selected rows: logical row i of piece t (start[t] <= i < start[t + 1]) lives at
 // staged row src[t] + (i - start[t]) (the pieces were packed in parallel, each at its own offset, and go
 // to the device in one DMA with the gaps).  n = 1, start = src = 0: rows in place.
-constexpr int kMaxPieces = 8;
-struct RowPieces {
+struct RowPieces {  // kMaxPieces: lio_pieces.hpp
     int n = 1;
     uint32_t start[kMaxPieces] = {};
     uint32_t src[kMaxPieces] = {};
@@ -71,7 +72,7 @@ struct FilterBuf {
     int64_t c_cap = 0;
     void* aux = nullptr;     // caller-side scratch (host API uploads)
     size_t aux_bytes = 0;
-    void* h_stage = nullptr; // pinned host staging of the sweep uploads (lio_capi stage_sweep)
+    void* h_stage = nullptr; // pinned host staging of the sweep uploads (lio_capi_prep.cpp)
     size_t stage_bytes = 0;
     int64_t prep_n = 0;      // row bound of the last scan_preprocess_enqueue (0: nothing pending)
     int64_t prep_sel = -1;   // its selected count when the host selected the rows (-1: on the device)
