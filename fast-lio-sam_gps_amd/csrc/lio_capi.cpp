@@ -43,4 +43,12 @@ int lio_abi_camera_struct_sizes(int64_t* out, int n) {
     return kN;
 }
 
+int lio_abi_overlay_struct_sizes(int64_t* out, int n) {
+    const int64_t sz[] = {(int64_t)sizeof(lio_overlay_params)};
+    constexpr int kN = (int)(sizeof(sz) / sizeof(sz[0]));
+    if (out)
+        for (int i = 0; i < n && i < kN; ++i) out[i] = sz[i];
+    return kN;
+}
+
 }  // extern "C"

@@ -1,16 +1,17 @@
 // lio_capi_camera.cpp — the C-ABI (include/lio_gpu.h) of the camera leg: lio_project_points and
-// lio_undistort_map on a lio_filter, the lio_colorizer, the lio_undistorter and the lio_exposure.
+// lio_undistort_map on a lio_filter, the lio_colorizer, the lio_undistorter, the lio_exposure and the lio_overlay.
 #include <limits>
 
 #include "lio_capi_util.hpp"
 #include "lio_colorize.hpp"
 #include "lio_exposure.hpp"
 #include "lio_overexposure.hpp"
+#include "lio_overlay.hpp"
 #include "lio_undistort.hpp"
 
 using namespace lio::capi;
 
-// ---- what the three frame handles share ----
+// ---- what the four frame handles share ----
 // The tail of a create: the buffers' init, and a handle whose init fails is closed again: *out stays NULL.
 template <class H, class Init>
 static int init_handle(H** out, const char* what, Init&& init, int (*destroy)(H*)) {
@@ -465,6 +466,150 @@ int lio_exposure_get_stencil_timing(lio_exposure* h, double* ms3) {
     const int rc = null_handle(h, "lio_exposure_get_stencil_timing");
     if (rc) return rc;
     return stage_times(h->e.stencil_timer, ms3);
+}
+
+// ---- point overlay drawing (lio_overlay.hip) ----
+static const lio_overlay_params kOverlayDefaults = {3, LIO_OVERLAY_DRAW_ORDER};
+static_assert(LIO_OVERLAY_DRAW_ORDER == lio::kOvDrawOrder && LIO_OVERLAY_NEAREST == lio::kOvNearest, "the order modes are the public ones");
+
+struct lio_overlay : Handle {
+    lio_overlay_params p = kOverlayDefaults;
+    lio::OvDisc disc = lio::overlay_disc(kOverlayDefaults.radius);
+    lio::OverlayBuf o;
+};
+
+int lio_overlay_destroy(lio_overlay* h) {
+    return close_handle(h, [](lio_overlay& z) { lio::overlay_free(z.o); });
+}
+
+// the device first (LIO_ERR_NODEV without one, whatever the params), then the params, then the handle
+int lio_overlay_create(int device, const lio_overlay_params* params, lio_overlay** out) {
+    const std::string what = "lio_overlay_create";
+    if (!out) return fail(LIO_ERR_ARG, what + ": out is NULL");
+    *out = nullptr;
+    int rc = check_device(device);
+    if (rc) return rc;
+    if (params && (params->radius < 0 || params->radius > lio::kOvMaxRadius)) return fail(LIO_ERR_ARG, what + ": radius must be in 0..15");
+    if (params && params->order != LIO_OVERLAY_DRAW_ORDER && params->order != LIO_OVERLAY_NEAREST)
+        return fail(LIO_ERR_ARG, what + ": order must be 0 (LIO_OVERLAY_DRAW_ORDER) or 1 (LIO_OVERLAY_NEAREST)");
+    if ((rc = open_handle(device, out, "lio_overlay_create: out is NULL"))) return rc;
+    if (params) (*out)->p = *params, (*out)->disc = lio::overlay_disc(params->radius);
+    return init_handle(out, what.c_str(), [](lio_overlay& z) { return lio::overlay_init(z.o, z.st); }, lio_overlay_destroy);
+}
+
+int lio_overlay_set_cloud(lio_overlay* h, const float* pts, int64_t n, int stride) {
+    const std::string what = "lio_overlay_set_cloud";
+    const int rc = null_handle(h, what.c_str());
+    if (rc) return rc;
+    if (n < 0 || n > lio::kOvMaxPoints) return fail(LIO_ERR_ARG, what + ": n must be in 0 .. 2^32 - 2");
+    if (stride < 3 || stride > lio::kMaxFields) return fail(LIO_ERR_ARG, what + ": stride must be in 3..8");
+    if (!pts && n > 0) return fail(LIO_ERR_ARG, what + ": pts is NULL");
+    HIP_TRY(hipSetDevice(h->dev));
+    return status(lio::overlay_set_cloud(h->o, pts, n, stride, h->st), what.c_str());
+}
+
+// what set_labels and set_colors share: the cloud is set, the values are as many as its points, and the other
+// per-point source is not set (exactly one colour source applies)
+static int overlay_source_arg(const std::string& what, const lio_overlay* h, const void* values, int64_t n, bool other,
+                              const char* other_name) {
+    if (!values) return LIO_OK;  // drops the source
+    if (!h->o.have_cloud) return fail(LIO_ERR_STATE, what + ": no cloud (call lio_overlay_set_cloud first)");
+    if (n != h->o.n) return fail(LIO_ERR_ARG, what + ": n must be the number of points of the cloud");
+    if (other) return fail(LIO_ERR_ARG, what + ": " + other_name + " are set: one colour source at a time (drop them with NULL first)");
+    return LIO_OK;
+}
+
+int lio_overlay_set_labels(lio_overlay* h, const int32_t* labels, int64_t n) {
+    const std::string what = "lio_overlay_set_labels";
+    int rc = null_handle(h, what.c_str());
+    if (rc) return rc;
+    if ((rc = overlay_source_arg(what, h, labels, n, h->o.have_colors, "per-point colours"))) return rc;
+    HIP_TRY(hipSetDevice(h->dev));
+    return status(lio::overlay_set_labels(h->o, labels, h->st), what.c_str());
+}
+
+int lio_overlay_set_colors(lio_overlay* h, const uint8_t* colors, int64_t n) {
+    const std::string what = "lio_overlay_set_colors";
+    int rc = null_handle(h, what.c_str());
+    if (rc) return rc;
+    if ((rc = overlay_source_arg(what, h, colors, n, h->o.have_labels, "labels"))) return rc;
+    HIP_TRY(hipSetDevice(h->dev));
+    return status(lio::overlay_set_colors(h->o, colors, h->st), what.c_str());
+}
+
+int lio_overlay_set_palette(lio_overlay* h, const uint8_t* palette, int32_t rows) {
+    const std::string what = "lio_overlay_set_palette";
+    const int rc = null_handle(h, what.c_str());
+    if (rc) return rc;
+    if (!palette) return fail(LIO_ERR_ARG, what + ": palette is NULL");
+    if (rows < 1) return fail(LIO_ERR_ARG, what + ": rows must be at least 1");
+    HIP_TRY(hipSetDevice(h->dev));
+    return status(lio::overlay_set_palette(h->o, palette, rows, h->st), what.c_str());
+}
+
+// the checks lio_overlay_draw and lio_overlay_draw_undistorted share, the handle's first; `image`: the call's name of it
+static int overlay_frame_arg(const std::string& what, const lio_overlay* h, const lio_camera* cam, const double* Rt,
+                             const uint8_t* image, const char* image_name, const uint8_t* out, const int64_t* n_drawn,
+                             lio::CamArg* a) {
+    int rc = null_handle(h, what.c_str());
+    if (rc) return rc;
+    if ((rc = camera_arg(what, cam, Rt, a))) return rc;
+    if (!image) return fail(LIO_ERR_ARG, what + ": " + image_name + " is NULL");
+    if (!out) return fail(LIO_ERR_ARG, what + ": out is NULL");
+    if (!n_drawn) return fail(LIO_ERR_ARG, what + ": n_drawn is NULL");
+    return LIO_OK;
+}
+
+// after the handle: the cloud is set, and the owner image's int32 holds every index of it
+static int overlay_state_arg(const std::string& what, const lio_overlay* h, const int32_t* owner_opt) {
+    if (!h->o.have_cloud) return fail(LIO_ERR_STATE, what + ": no cloud (call lio_overlay_set_cloud first)");
+    if (owner_opt && h->o.n > (int64_t)std::numeric_limits<int32_t>::max())
+        return fail(LIO_ERR_ARG, what + ": owner_opt holds int32 indices: the cloud must have fewer than 2^31 points");
+    return LIO_OK;
+}
+
+int lio_overlay_draw(lio_overlay* h, const lio_camera* cam, const double* Rt, const uint8_t* image, int64_t pitch, uint8_t* out,
+                     int64_t out_pitch, int32_t* owner_opt, int64_t* n_drawn) {
+    const std::string what = "lio_overlay_draw";
+    lio::CamArg a{};
+    int rc = overlay_frame_arg(what, h, cam, Rt, image, "image", out, n_drawn, &a);
+    if (rc) return rc;
+    if ((rc = pitch_arg(what, "pitch", pitch, 3, cam->width))) return rc;
+    if ((rc = pitch_arg(what, "out_pitch", out_pitch, 3, cam->width))) return rc;
+    if ((rc = overlay_state_arg(what, h, owner_opt))) return rc;
+    *n_drawn = 0;
+    HIP_TRY(hipSetDevice(h->dev));
+    return status(lio::overlay_draw(h->o, nullptr, a, h->disc, h->p.order, image, pitch, out, out_pitch, owner_opt, n_drawn, h->st),
+                  what.c_str());
+}
+
+int lio_overlay_draw_undistorted(lio_overlay* h, lio_undistorter* undistorter, const lio_camera* cam, const double* Rt,
+                                 const uint8_t* raw_image, int64_t pitch, uint8_t* out, int64_t out_pitch, int32_t* owner_opt,
+                                 int64_t* n_drawn) {
+    const std::string what = "lio_overlay_draw_undistorted";
+    lio::CamArg a{};
+    int rc = overlay_frame_arg(what, h, cam, Rt, raw_image, "raw_image", out, n_drawn, &a);
+    if (rc) return rc;
+    if (!undistorter) return fail(LIO_ERR_ARG, what + ": undistorter is NULL");
+    if (undistorter->dev != h->dev) return fail(LIO_ERR_ARG, what + ": both handles must be on one device");
+    lio::UndistortBuf& u = undistorter->u;
+    if ((rc = undistorter_frame_arg(what, u, pitch, out_pitch))) return rc;
+    if (u.channels != 3) return fail(LIO_ERR_ARG, what + ": the undistorter must be set up for 3 channels");
+    if (cam->width != u.dw || cam->height != u.dh)
+        return fail(LIO_ERR_ARG, what + ": cam's width and height must be those of the undistorter's rectified image");
+    if ((rc = overlay_state_arg(what, h, owner_opt))) return rc;
+    *n_drawn = 0;
+    HIP_TRY(hipSetDevice(h->dev));
+    // as in lio_exposure_clahe_undistorted: the undistorter's buffers are used on h's stream
+    return status(lio::overlay_draw(h->o, &u, a, h->disc, h->p.order, raw_image, pitch, out, out_pitch, owner_opt, n_drawn, h->st),
+                  what.c_str());
+}
+
+int lio_overlay_get_timing(lio_overlay* h, double* ms5) {
+    const int rc = null_handle(h, "lio_overlay_get_timing");
+    if (rc) return rc;
+    if (!ms5) return fail(LIO_ERR_ARG, "lio_overlay_get_timing: ms5 is NULL");
+    return stage_times(h->o.timer, ms5);
 }
 
 }  // extern "C"

@@ -5,8 +5,8 @@
 // (include/lio_gpu.h: lio_project_points, lio_colorizer_*).  The file is compiled with -ffp-contract=off, host
 // and device: no multiply-add is fused anywhere.
 //
-// One thread per point everywhere.  cz_project is the ONLY projection: the project, fused, splat and resolve
-// kernels all call it, so a point's pixel and depth are the same bits in every pass.
+// One thread per point everywhere.  cz_project (lio_camera_dev.hpp) is the ONLY projection: the project, fused,
+// splat and resolve kernels all call it, so a point's pixel and depth are the same bits in every pass.
 //   without occlusion  cz_fused_kernel: project, gather the pixel, replace the state where zc < best_z
 //   with occlusion     cz_fill_kernel (the depth image to the bits of +inf) -> cz_splat_kernel (atomicMin of the
 //                      float depth's bits over the clipped splat) -> cz_resolve_kernel (project again, the
@@ -24,31 +24,6 @@
 namespace lio {
 
 namespace {
-
-struct Projected {
-    double u, v, zc;
-    int px, py;  // -1 where invalid
-    bool valid;
-};
-
-// the contract's projection (include/lio_gpu.h, lio_project_points), one operation per line of it
-__device__ __forceinline__ Projected cz_project(const float* __restrict__ p, const CamArg& c) {
-    const double x = (double)p[0], y = (double)p[1], z = (double)p[2];
-    const double xc = ((c.R[0] * x + c.R[1] * y) + c.R[2] * z) + c.t[0];
-    const double yc = ((c.R[3] * x + c.R[4] * y) + c.R[5] * z) + c.t[1];
-    const double zc = ((c.R[6] * x + c.R[7] * y) + c.R[8] * z) + c.t[2];
-    const double xn = xc / zc, yn = yc / zc;
-    const Distorted d = cam_distort(xn, yn, c);  // r2 ... u, v: shared with the undistortion map (lio_camera_dev.hpp)
-    Projected o;
-    o.u = d.u;
-    o.v = d.v;
-    o.zc = zc;
-    // every comparison is false on NaN
-    o.valid = zc > 0.0 && d.r2 <= c.r2_max && o.u >= 0.0 && o.u < (double)c.width && o.v >= 0.0 && o.v < (double)c.height;
-    o.px = o.valid ? (int)o.u : -1;  // truncation only after the test: u = -0.5 is invalid, not pixel 0
-    o.py = o.valid ? (int)o.v : -1;
-    return o;
-}
 
 __global__ __launch_bounds__(256) void cz_project_kernel(const float* __restrict__ pts, int64_t n, int stride, CamArg cam,
                                                          double2* __restrict__ uv, double* __restrict__ zc,

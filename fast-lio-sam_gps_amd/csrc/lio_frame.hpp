@@ -1,5 +1,5 @@
-// lio_frame.hpp — the host path of one camera frame, shared by the camera leg's three handles (ColorizeBuf,
-// UndistortBuf, ExposureBuf).  Host only, header only.
+// lio_frame.hpp — the host path of one camera frame, shared by the camera leg's four handles (ColorizeBuf,
+// UndistortBuf, ExposureBuf, OverlayBuf).  Host only, header only.
 //   frame_span, frame_pitch, copy_rows              the byte arithmetic of a pitched image and the copy to a caller's rows
 //   FrameStage, reserve_frames                      a device buffer and its pinned twin: reserve, upload, download, free
 //   StageTimer<N>                                   the events of N stages and their times in ms

@@ -29,6 +29,7 @@ LIO_GPSALIGN_LEN = 25
  GPSALIGN_TOTAL_SCALE, GPSALIGN_TOTAL_C, GPSALIGN_TOTAL_S, GPSALIGN_TOTAL_T) = (
     0, 1, 2, 3, 4, 6, 8, 9, 10, 11, 13, 15, 16, 17, 18, 20, 21, 22, 23)
 LIO_SIM2D_LEN = 5
+LIO_OVERLAY_DRAW_ORDER, LIO_OVERLAY_NEAREST = 0, 1
 
 # Every symbol include/lio_gpu.h declares (checked by tests/test_capi_symbols.py).
 EXPORTS = [
@@ -65,6 +66,9 @@ EXPORTS = [
     "lio_exposure_clahe_undistorted", "lio_exposure_get_timing",
     "lio_gaussian_weights", "lio_exposure_gaussian_blur", "lio_exposure_recover", "lio_exposure_recover_undistorted",
     "lio_exposure_get_stencil_timing",
+    "lio_abi_overlay_struct_sizes", "lio_overlay_create", "lio_overlay_destroy", "lio_overlay_set_cloud",
+    "lio_overlay_set_labels", "lio_overlay_set_colors", "lio_overlay_set_palette", "lio_overlay_draw",
+    "lio_overlay_draw_undistorted", "lio_overlay_get_timing",
 ]
 
 
@@ -165,6 +169,10 @@ class ColorizeParams(C.Structure):
 
 class RecoverParams(C.Structure):  # lio_recover_params
     _fields_ = [("threshold", C.c_int), ("dilate", C.c_int), ("ksize", C.c_int), ("sigma", C.c_double)]
+
+
+class OverlayParams(C.Structure):  # lio_overlay_params
+    _fields_ = [("radius", C.c_int32), ("order", C.c_int32)]
 
 
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.POINTER(C.c_double), C.c_int64, C.POINTER(C.c_double), C.c_void_p)
@@ -295,6 +303,18 @@ def _declare(L):
                                            C.c_int64]),
         "lio_exposure_recover_undistorted": (C.c_int, [vp, vp, vp, C.c_int64, C.c_int, C.POINTER(RecoverParams), vp, C.c_int64]),
         "lio_exposure_get_stencil_timing": (C.c_int, [vp, dp]),
+        "lio_abi_overlay_struct_sizes": (C.c_int, [C.POINTER(C.c_int64), C.c_int]),
+        "lio_overlay_create": (C.c_int, [C.c_int, C.POINTER(OverlayParams), C.POINTER(vp)]),
+        "lio_overlay_destroy": (C.c_int, [vp]),
+        "lio_overlay_set_cloud": (C.c_int, [vp, fp, C.c_int64, C.c_int]),
+        "lio_overlay_set_labels": (C.c_int, [vp, C.POINTER(C.c_int32), C.c_int64]),
+        "lio_overlay_set_colors": (C.c_int, [vp, C.POINTER(C.c_uint8), C.c_int64]),
+        "lio_overlay_set_palette": (C.c_int, [vp, C.POINTER(C.c_uint8), C.c_int32]),
+        "lio_overlay_draw": (C.c_int, [vp, C.POINTER(Camera), dp, vp, C.c_int64, vp, C.c_int64, C.POINTER(C.c_int32),
+                                       C.POINTER(C.c_int64)]),
+        "lio_overlay_draw_undistorted": (C.c_int, [vp, vp, C.POINTER(Camera), dp, vp, C.c_int64, vp, C.c_int64,
+                                                   C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+        "lio_overlay_get_timing": (C.c_int, [vp, dp]),
         "lio_ctx_create": (C.c_int, [vp, C.POINTER(MatchParams), C.POINTER(vp)]),
         "lio_ctx_destroy": (C.c_int, [vp]),
         "lio_scan_set": (C.c_int, [vp, fp, C.c_int64]),
@@ -395,28 +415,26 @@ _ABI_STRUCTS = ("MapParams", "MatchParams", "Pose", "State", "IeskfParams", "Ies
                 "LocalMap", "IncrementalStats", "ImuPose", "ScanPrepParams", "CloudField", "KernelTiming", "DenoiseParams")
 # likewise of lio_abi_camera_struct_sizes (the first list is closed: callers compare its length)
 _ABI_CAMERA_STRUCTS = ("Camera", "ColorizeParams")
+# and of lio_abi_overlay_struct_sizes (the second list is closed too)
+_ABI_OVERLAY_STRUCTS = ("OverlayParams",)
 
 
 def _check_abi(L):
     """Refuse a library whose public structs differ from these mirrors: an output struct of another size
     overruns the caller's buffer (how round 4's LIO_GPU_LIB A/B against a round-2 build corrupted the heap:
     its lio_kernel_timing carried an extra finalize pair, 128 bytes written into a 112-byte ctypes struct)."""
-    n = int(L.lio_abi_struct_sizes(None, 0))
-    sizes = (C.c_int64 * n)()
-    L.lio_abi_struct_sizes(sizes, n)
-    mine = [C.sizeof(globals()[k]) for k in _ABI_STRUCTS]
-    if n != len(mine) or list(sizes) != mine:
-        raise ImportError(f"{LIB_PATH}: ABI mismatch with lio_gpu/_capi.py — library struct sizes {list(sizes)}, "
-                          f"binding {mine} ({', '.join(_ABI_STRUCTS)})")
-    if not hasattr(L, "lio_abi_camera_struct_sizes"):  # an older build (LIO_GPU_LIB) has no camera entry points
-        return
-    n = int(L.lio_abi_camera_struct_sizes(None, 0))
-    sizes = (C.c_int64 * n)()
-    L.lio_abi_camera_struct_sizes(sizes, n)
-    mine = [C.sizeof(globals()[k]) for k in _ABI_CAMERA_STRUCTS]
-    if n != len(mine) or list(sizes) != mine:
-        raise ImportError(f"{LIB_PATH}: ABI mismatch with lio_gpu/_capi.py — library struct sizes {list(sizes)}, "
-                          f"binding {mine} ({', '.join(_ABI_CAMERA_STRUCTS)})")
+    # an older build (LIO_GPU_LIB) has no camera entry points, or none of the overlay's
+    for fn, names in (("lio_abi_struct_sizes", _ABI_STRUCTS), ("lio_abi_camera_struct_sizes", _ABI_CAMERA_STRUCTS),
+                      ("lio_abi_overlay_struct_sizes", _ABI_OVERLAY_STRUCTS)):
+        if fn != "lio_abi_struct_sizes" and not hasattr(L, fn):
+            return
+        n = int(getattr(L, fn)(None, 0))
+        sizes = (C.c_int64 * n)()
+        getattr(L, fn)(sizes, n)
+        mine = [C.sizeof(globals()[k]) for k in names]
+        if n != len(mine) or list(sizes) != mine:
+            raise ImportError(f"{LIB_PATH}: ABI mismatch with lio_gpu/_capi.py — library struct sizes {list(sizes)}, "
+                              f"binding {mine} ({', '.join(names)})")
 
 
 def check(rc):

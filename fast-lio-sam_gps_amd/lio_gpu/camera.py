@@ -10,6 +10,9 @@ over the C-ABI.
 * :func:`undistort_map`, :class:`Undistorter`, :func:`undistort_image` — the scripts' ``cv2.undistort(img, K, D, None,
   K)`` on every frame (post_process/undistort_image.py:21-27), as a 1/32-pixel map and an integer bilinear gather
   (``lio_undistort_map``, ``lio_undistorter_*``); :meth:`CameraModel.rectified` is the camera of its output
+* :class:`PointOverlay`, :func:`draw_points` — the image with every projected point drawn as a filled disc, the
+  output of the reference's projection tool (post_process/lidar_projection/src/lidar_projection.cpp:113-125;
+  ``lio_overlay_*``); :func:`lidar_projection_overlay` — that tool from its k-means to the finished image
 
 Images are numpy arrays (``height x width x 3`` uint8); decoding them is the caller's.  Every result follows the
 contract of include/lio_gpu.h bit for bit: IEEE double operations in a written order, nothing fused.
@@ -361,3 +364,170 @@ def colorize_pcd(in_path: str, image, camera: CameraModel, Rt, out_path: str, de
     rec[:, 3] = pack_rgb(rgb)
     formats.write_pcd_binary(out_path, rec, names=("x", "y", "z", "rgb"))
     return len(xyz), int(np.count_nonzero(np.asarray(frame) >= 0))
+
+
+ORDERS = {"draw": _capi.LIO_OVERLAY_DRAW_ORDER, "nearest": _capi.LIO_OVERLAY_NEAREST}
+
+
+def _overlay_params(radius, order) -> _capi.OverlayParams:
+    if int(radius) != radius or not 0 <= radius <= 15:
+        raise ValueError("radius: an integer in 0..15 is expected")
+    if order not in ORDERS:
+        raise ValueError("order: 'draw' (later points over earlier ones) or 'nearest' (the nearest point wins) is expected")
+    return _capi.OverlayParams(int(radius), ORDERS[order])
+
+
+def _per_point(a, n: int, dtype, cols: int, what: str) -> np.ndarray:
+    """``a`` as it goes to the library: exactly ``dtype`` (nothing is cast: a float label is a mistake), one value per
+    point (``cols`` 0) or ``cols`` of them"""
+    a = np.asarray(a)
+    if a.dtype != dtype:
+        raise ValueError(f"{what}: dtype {np.dtype(dtype).name} is expected, not {a.dtype.name}")
+    if a.shape != ((n, cols) if cols else (n,)):
+        raise ValueError(f"{what}: shape {(n, cols) if cols else (n,)} is expected (one per point), not {a.shape}")
+    return np.ascontiguousarray(a)
+
+
+def _palette(palette) -> np.ndarray:
+    p = np.asarray(palette)
+    if p.dtype != np.uint8 or p.ndim != 2 or p.shape[1] != 3 or len(p) < 1:
+        raise ValueError("palette: a P x 3 uint8 array with P >= 1 is expected")
+    return np.ascontiguousarray(p)
+
+
+def _colour_sources(n: int, labels, colors, palette):
+    """the checked (labels, colors, palette) of a draw, each None where not given.  Exactly one source applies:
+    ``colors``; or ``labels`` through ``palette``; or ``palette``'s row 0 (none: the handle's, green at first)"""
+    if colors is not None and (labels is not None or palette is not None):
+        raise ValueError("more than one colour source: give colors, or labels (with a palette), or a palette alone")
+    return (_per_point(labels, n, np.int32, 0, "labels") if labels is not None else None,
+            _per_point(colors, n, np.uint8, 3, "colors") if colors is not None else None,
+            _palette(palette) if palette is not None else None)
+
+
+class PointOverlay(_Handle):
+    """The projection tool's output: every valid point of a cloud drawn on the image as a filled disc of ``radius``
+    pixels (OpenCV's filled midpoint circle around the centre rounded to even, clipped to the image).  ``order="draw"``:
+    later points over earlier ones, the tool's sequential loop; ``order="nearest"``: the nearest point wins a pixel.
+    The colour of a point is three bytes in the image's own channel order: ``set_colors`` (one per point), or
+    ``set_labels`` through ``set_palette`` (``palette[label % P]``; a point with a negative label is not drawn), or
+    the palette's first row for every point (green at first, as the tool ships).  The cloud and the colour sources
+    stay on the device between frames.  Every result follows the contract of include/lio_gpu.h bit for bit
+    (agreement of the disc with OpenCV is a reading of its source, not a test)."""
+
+    _create, _destroy = "lio_overlay_create", "lio_overlay_destroy"
+
+    def __init__(self, radius: int = 3, order: str = "draw", device: int = 0):
+        self._n = None
+        p = _overlay_params(radius, order)
+        super().__init__(device, C.byref(p))
+        self.n_drawn = 0
+
+    def set_cloud(self, pts):
+        """uploads the cloud; the labels and per-point colours of the cloud before it are dropped"""
+        p = _rows(pts)
+        self._n = None
+        check(lib().lio_overlay_set_cloud(self._h, _fp(p), len(p), p.shape[1]))
+        self._n = len(p)
+
+    def _need_cloud(self):
+        if self._n is None:  # the library's state error, with its message
+            check(lib().lio_overlay_set_labels(self._h, np.zeros(1, np.int32).ctypes.data_as(C.POINTER(C.c_int32)), 1))
+
+    def set_labels(self, labels):
+        """one int32 per point (none: dropped); negative: that point is not drawn"""
+        self._need_cloud()
+        a = _per_point(labels, self._n, np.int32, 0, "labels") if labels is not None else None
+        check(lib().lio_overlay_set_labels(self._h, a.ctypes.data_as(C.POINTER(C.c_int32)) if a is not None else None,
+                                           self._n if a is not None else 0))
+
+    def set_colors(self, colors):
+        """three uint8 per point in the image's channel order (none: dropped)"""
+        self._need_cloud()
+        a = _per_point(colors, self._n, np.uint8, 3, "colors") if colors is not None else None
+        check(lib().lio_overlay_set_colors(self._h, a.ctypes.data_as(C.POINTER(C.c_uint8)) if a is not None else None,
+                                           self._n if a is not None else 0))
+
+    def set_palette(self, palette):
+        p = _palette(palette)
+        check(lib().lio_overlay_set_palette(self._h, p.ctypes.data_as(C.POINTER(C.c_uint8)), len(p)))
+
+    def _draw(self, entry, head, camera, Rt, src, pitch, out, owner):
+        rt = _pose(Rt)
+        cam = camera._c()
+        out, o = _out(out, (camera.height, camera.width, 3), 3, camera.width)
+        own = np.empty((camera.height, camera.width), np.int32) if owner else None
+        n = C.c_int64(0)
+        check(entry(self._h, *head, C.byref(cam), rt.ctypes.data_as(_dp), src.ctypes.data_as(C.c_void_p), pitch,
+                    o.ctypes.data_as(C.c_void_p), o.strides[0], own.ctypes.data_as(C.POINTER(C.c_int32)) if owner else None,
+                    C.byref(n)))
+        self.n_drawn = int(n.value)
+        return (out, own) if owner else out
+
+    def draw(self, camera: CameraModel, Rt, image, out=None, owner: bool = False):
+        """the drawn image (``out``: a uint8 array of the image's shape to write into; its rows may be padded, the
+        padding is not touched; it may be ``image``); with ``owner`` also the ``height x width`` int32 image of each
+        pixel's owning point, -1 where none.  ``n_drawn``: the points that were valid and not skipped by their label."""
+        img, pitch = _image(image, camera)
+        return self._draw(lib().lio_overlay_draw, (), camera, Rt, img, pitch, out, owner)
+
+    def draw_undistorted(self, undistorter: Undistorter, camera: CameraModel, Rt, raw_image, out=None, owner: bool = False):
+        """``undistorter(raw_image)`` then :meth:`draw`, bit for bit, with one upload and one download.  ``camera``: the
+        rectified image's (:meth:`CameraModel.rectified`)."""
+        if undistorter._shape is None:  # the library's state error, with its message
+            return self._draw(lib().lio_overlay_draw_undistorted, (undistorter._h,), camera, Rt, np.zeros(1, np.uint8), 0, out,
+                              owner)
+        sh, sw = undistorter._shape[:2]
+        img, pitch, ch = _plane(raw_image, sw, sh, "raw_image")
+        if ch != 3:
+            raise ValueError("raw_image: a height x width x 3 uint8 array is expected")
+        return self._draw(lib().lio_overlay_draw_undistorted, (undistorter._h,), camera, Rt, img, pitch, out, owner)
+
+    def timing(self) -> dict:
+        """device ms of the last draw: upload (staging copy included), fill, stamp, compose, download"""
+        return self._timing("lio_overlay_get_timing", ("upload_ms", "fill_ms", "stamp_ms", "compose_ms", "download_ms"))
+
+
+def draw_points(image, pts, camera: CameraModel, Rt, radius: int = 3, order: str = "draw", labels=None, colors=None,
+                palette=None, owner: bool = False):
+    """one image through a fresh :class:`PointOverlay` (for many frames of one cloud keep the handle): ``pts`` drawn
+    on ``image`` as filled discs.  One colour source: ``colors`` (n x 3 uint8, e.g. ``filters.cluster_palette(labels)``),
+    or ``labels`` (n int32) with a ``palette`` (P x 3 uint8; none: green), or ``palette``'s first row for every point
+    (none: green, as the tool ships).  Returns the drawn image, with ``owner`` also the owner image.  Every argument is
+    checked before the device is touched."""
+    p = _rows(pts)
+    _overlay_params(radius, order)
+    labels, colors, palette = _colour_sources(len(p), labels, colors, palette)
+    _image(image, camera)
+    ov = PointOverlay(radius, order)
+    try:
+        ov.set_cloud(p)
+        if palette is not None:
+            ov.set_palette(palette)
+        if labels is not None:
+            ov.set_labels(labels)
+        if colors is not None:
+            ov.set_colors(colors)
+        return ov.draw(camera, Rt, image, owner=owner)
+    finally:
+        ov.close()
+
+
+def lidar_projection_overlay(pts, image, camera: CameraModel, Rt, K: int = 5, seed: int = 0, by_cluster: bool = False,
+                             radius: int = 3):
+    """The ``main`` of post_process/lidar_projection/src/lidar_projection.cpp from its k-means to the finished image
+    (:82-125): :class:`lio_gpu.filters.KMeans` with the tool's criteria, :func:`lio_gpu.filters.cluster_palette`, then
+    the overlay in draw order.  ``by_cluster=False`` is the tool as shipped: its palette call is commented out and
+    every point is drawn green (0, 255, 0); ``True`` draws each point in its cluster's colour (B G R, for OpenCV's
+    image).  Returns ``(drawn image, labels)``."""
+    from . import filters
+
+    p = _rows(pts)
+    km = filters.KMeans(n_clusters=K, seed=seed)
+    try:
+        labels = km.fit(p)
+    finally:
+        km.close()
+    if by_cluster:
+        return draw_points(image, p, camera, Rt, radius=radius, colors=filters.cluster_palette(labels)), labels
+    return draw_points(image, p, camera, Rt, radius=radius), labels

@@ -380,7 +380,8 @@ CLUSTER_PALETTE_BGR = np.array([(255, 0, 0), (0, 255, 0), (0, 0, 255), (255, 255
 
 def cluster_palette(labels) -> np.ndarray:
     """n x 3 uint8 B, G, R: the projection tool's colour of each point's cluster (``label % 10``), black for -1.
-    Host only; the drawing itself is the caller's."""
+    Host only.  :func:`lio_gpu.camera.draw_points` draws with it (``colors=``), and
+    :func:`lio_gpu.camera.lidar_projection_overlay` is the tool from its k-means to the finished image."""
     lab = np.asarray(labels).astype(np.int64).reshape(-1)
     out = CLUSTER_PALETTE_BGR[np.mod(lab, 10)]
     out[lab < 0] = 0

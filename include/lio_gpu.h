@@ -958,6 +958,78 @@ int lio_ctx_reset_timing(lio_ctx* c);
 int lio_icp_set_timing(lio_icp* h, int enable);
 int lio_icp_get_timing(lio_icp* h, lio_kernel_timing* out);
 
+/* ------------------------------------------------------ point overlay drawing (filled discs; offline camera leg) */
+/* The output of the reference's projection tool (post_process/lidar_projection/src/lidar_projection.cpp:113-125): the
+ * camera image with every projected point drawn as a filled cv::circle of 3 pixels, later points over earlier ones.
+ * The contract is the library's own, exact to the bit.
+ *   inputs   the colorizer's point records (n x stride float32, stride 3..8, x y z first; 0 <= n <= 2^32 - 2), a
+ *            lio_camera and a pose Rt of 12 doubles, an image of height x width x 3 uint8 with a row pitch, a radius
+ *            r in 0..15, an order mode, one colour source.
+ *   project  lio_project_points above, with distortion and r2_max: u, v, zc and valid are its bits (one device
+ *            function serves both).  The tool's float (K p) / p_z is another rounding and is NOT reproduced.
+ *   centre   cxi = (int)rint(u), cyi = (int)rint(v) in double, TIES TO EVEN, which is what cv::circle does to a
+ *            Point2f.  THE CENTRE IS ROUNDED ONLY AFTER THE VALIDITY TEST on the unrounded u, v: a valid point may get
+ *            a centre at x == width or y == height.  THE DISC IS CLIPPED TO THE IMAGE, NEVER WRAPPED.
+ *   disc     the pixel set of OpenCV's filled midpoint circle: dx = r, dy = 0, err = 0, plus = 1, minus = 2 r - 1;
+ *            while dx >= dy: the rows cy +- dy take the columns cx - dx .. cx + dx and the rows cy +- dx the columns
+ *            cx - dy .. cx + dy; then dy += 1; err += plus; plus += 2; if err > 0: err -= minus; dx -= 1; minus -= 2.
+ *            Equivalently ONE HALF-WIDTH PER |ROW OFFSET|: r = 0: {0} (1 pixel); 1: {1, 0} (5); 2: {2, 1, 0} (13);
+ *            3: {3, 2, 2, 0} (29); 4: {4, 3, 3, 2, 0} (49).  The table of the call's r is built on the host; the
+ *            kernel holds no circle logic.  AGREEMENT WITH cv2.circle IS OUR READING OF ITS SOURCE AND IS UNVERIFIED:
+ *            OpenCV was not available where this was written.
+ *   owner    each pixel has one 64-bit key, all ones where empty.  Each drawn point i puts
+ *            key_i = (hi << 32) | (0xFFFFFFFF - i) on every pixel of its clipped disc and THE MINIMUM STAYS.
+ *            LIO_OVERLAY_DRAW_ORDER: hi = 0, so the highest index wins: exactly the tool's sequential loop, where
+ *            later circles overwrite earlier ones.  LIO_OVERLAY_NEAREST: hi = the bits of (float)zc, rounded to
+ *            nearest; zc > 0, so unsigned order is float order: the nearest point wins, and ON EQUAL FLOAT DEPTH THE
+ *            HIGHER INDEX WINS.  One code path; the result does not depend on the device's schedule.
+ *   colour   three bytes in the image's own channel order, NO SWIZZLE.  Exactly one source applies: per-point colours
+ *            (n x 3 uint8) if set; otherwise labels (n int32) with the palette of P >= 1 rows: A POINT WITH label < 0
+ *            IS NOT DRAWN AT ALL AND OWNS NOTHING, any other takes palette[label % P]; otherwise the palette's row 0
+ *            for every point.  The palette starts as the one row 0 255 0: the tool as shipped draws every point green.
+ *   outputs  out: each owned pixel is its owner's colour, EVERY OTHER PIXEL BYTE FOR BYTE THE INPUT'S; only 3 x width
+ *            bytes of a row are read or written: the padding of the caller's rows is left untouched (out may be
+ *            image).  owner_opt (may be NULL): height x width int32, the owning point's index or -1; it needs
+ *            n < 2^31.  n_drawn: the number of points that were valid and not skipped by their label.
+ * lio_overlay: the cloud, labels, per-point colours and palette stay on the device between frames.  set_cloud drops
+ *   the labels and per-point colours of the cloud before it.  set_labels / set_colors: n is the cloud's; NULL drops
+ *   the source; setting one while the other is set is LIO_ERR_ARG.  params NULL means {3, LIO_OVERLAY_DRAW_ORDER}.
+ * lio_overlay_draw_undistorted: the undistorter's configured 3-channel frame is rectified and drawn on with ONE UPLOAD
+ *   AND ONE DOWNLOAD; the result equals lio_undistorter_run followed by lio_overlay_draw bit for bit (the tool reads
+ *   rectified images: this is its real path).  cam: the rectified image's camera, of the undistorter's output size;
+ *   pitch: the raw image's.  Both handles must be on one device.
+ * lio_overlay_get_timing: device ms of the last draw from stream events: upload (its staging copy included; in the
+ *   chained call the undistorter's upload and gather), fill, stamp, compose, download.
+ * The handle is looked at first: every entry is LIO_ERR_NODEV without a device (there is no CPU path).  LIO_ERR_ARG
+ * before any device work, with a message that names the bound: a NULL out, cam, Rt, image, n_drawn, palette or ms5
+ * (pts may be NULL when n == 0), a radius outside 0..15, an order that is neither mode, n < 0 or > 2^32 - 2, stride
+ * outside 3..8, an n of labels or colours that is not the cloud's, rows < 1, the camera and pose conditions of
+ * lio_project_points, pitch or out_pitch < 3 x width, owner_opt with n >= 2^31.  LIO_ERR_STATE: labels, colours or a
+ * draw before set_cloud.  From the second frame of one size on nothing is allocated (lio_alloc_count); repeated draws
+ * give identical bits.                                                                                              */
+#define LIO_OVERLAY_DRAW_ORDER 0
+#define LIO_OVERLAY_NEAREST 1
+typedef struct lio_overlay_params {
+    int32_t radius; /* 0..15; the tool: 3 */
+    int32_t order;  /* LIO_OVERLAY_DRAW_ORDER (the tool) or LIO_OVERLAY_NEAREST */
+} lio_overlay_params;
+/* sizeof of the struct above, a third list as lio_abi_camera_struct_sizes is the second (both earlier lists are
+ * closed: callers compare their lengths); returns the number of its entries.                                     */
+int lio_abi_overlay_struct_sizes(int64_t* out, int n);
+typedef struct lio_overlay lio_overlay;
+int lio_overlay_create(int device, const lio_overlay_params* params, lio_overlay** out);
+int lio_overlay_destroy(lio_overlay* h);
+int lio_overlay_set_cloud(lio_overlay* h, const float* pts, int64_t n, int stride);
+int lio_overlay_set_labels(lio_overlay* h, const int32_t* labels, int64_t n);
+int lio_overlay_set_colors(lio_overlay* h, const uint8_t* colors, int64_t n);
+int lio_overlay_set_palette(lio_overlay* h, const uint8_t* palette, int32_t rows);
+int lio_overlay_draw(lio_overlay* h, const lio_camera* cam, const double* Rt, const uint8_t* image, int64_t pitch, uint8_t* out,
+                     int64_t out_pitch, int32_t* owner_opt, int64_t* n_drawn);
+int lio_overlay_draw_undistorted(lio_overlay* h, lio_undistorter* undistorter, const lio_camera* cam, const double* Rt,
+                                 const uint8_t* raw_image, int64_t pitch, uint8_t* out, int64_t out_pitch, int32_t* owner_opt,
+                                 int64_t* n_drawn);
+int lio_overlay_get_timing(lio_overlay* h, double* ms5);
+
 /* -------------------------------------------------------- exposure adaption (CLAHE on V, table remaps; camera leg) */
 /* What the reference runs on every rectified frame: post_process/exposure_adaption/CLAHE_region_adjusted.py:6-41
  * (adapt_exposure: BGR -> HSV, CLAHE of V with clip 2.0 and 8 x 8 tiles, HSV -> BGR) and correct_exposure:6-103

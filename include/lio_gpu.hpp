@@ -940,6 +940,81 @@ private:
     int sw_ = 0, dw_ = 0, channels_ = 3;
 };
 
+// The output of the reference's projection tool (lio_overlay): the image with every valid point of a cloud drawn as
+// a filled disc (post_process/lidar_projection/src/lidar_projection.cpp:113-125), in the shape of the filters:
+// setInputCloud / setLabels / setColors / setPalette / draw.  The colour of a point is three bytes in the image's own
+// channel order: setColors (one per point), else setLabels through setPalette (palette[label % P]; a negative label
+// is not drawn), else the palette's first row (green at first, as the tool ships).
+template <typename PointT>
+class PointOverlay {
+public:
+    // radius 0..15 (the tool: 3); nearest: the nearest point wins a pixel (false: later points over earlier ones)
+    explicit PointOverlay(int radius = 3, bool nearest = false, int device = 0) {
+        const lio_overlay_params p{radius, nearest ? LIO_OVERLAY_NEAREST : LIO_OVERLAY_DRAW_ORDER};
+        check(lio_overlay_create(device, &p, &h_), "lio_overlay_create");
+    }
+    ~PointOverlay() { lio_overlay_destroy(h_); }
+    PointOverlay(const PointOverlay&) = delete;
+    PointOverlay& operator=(const PointOverlay&) = delete;
+    // the labels and per-point colours of the cloud before it are dropped
+    void setInputCloud(const std::vector<PointT>* cloud) {
+        if (!cloud) throw Error(LIO_ERR_ARG, "PointOverlay: no input cloud");
+        check(lio_overlay_set_cloud(h_, reinterpret_cast<const float*>(cloud->data()), (int64_t)cloud->size(),
+                                    float_stride<PointT>()),
+              "PointOverlay::setInputCloud");
+    }
+    // one per point of the cloud; null: dropped
+    void setLabels(const std::vector<int32_t>* labels) {
+        check(lio_overlay_set_labels(h_, labels ? labels->data() : nullptr, labels ? (int64_t)labels->size() : 0),
+              "PointOverlay::setLabels");
+    }
+    // three bytes per point of the cloud; null: dropped
+    void setColors(const std::vector<uint8_t>* colors) {
+        check(lio_overlay_set_colors(h_, colors ? colors->data() : nullptr, colors ? (int64_t)(colors->size() / 3) : 0),
+              "PointOverlay::setColors");
+    }
+    void setPalette(const std::vector<std::array<uint8_t, 3>>& palette) {
+        check(lio_overlay_set_palette(h_, palette.empty() ? nullptr : palette[0].data(), (int32_t)palette.size()),
+              "PointOverlay::setPalette");
+    }
+    // image -> out: height rows of `pitch` / `out_pitch` bytes (0: 3 * width), out may be image; owner_opt: height x
+    // width, the owning point of each pixel, -1: none.  Returns the points drawn.
+    int64_t draw(const CameraModel& cam, const std::array<double, 12>& Rt, const uint8_t* image, uint8_t* out, int64_t pitch = 0,
+                 int64_t out_pitch = 0, std::vector<int32_t>* owner_opt = nullptr) {
+        const lio_camera c = cam.c();
+        int64_t drawn = 0;
+        check(lio_overlay_draw(h_, &c, Rt.data(), image, pitch ? pitch : 3 * (int64_t)cam.width, out,
+                               out_pitch ? out_pitch : 3 * (int64_t)cam.width, owner_image(cam, owner_opt), &drawn),
+              "PointOverlay::draw");
+        return drawn;
+    }
+    // ud.undistort(raw) then draw, bit for bit, with one upload and one download; cam: the rectified image's
+    int64_t drawUndistorted(Undistorter& ud, const CameraModel& cam, const std::array<double, 12>& Rt, const uint8_t* raw,
+                            uint8_t* out, int64_t pitch = 0, int64_t out_pitch = 0, std::vector<int32_t>* owner_opt = nullptr) {
+        const lio_camera c = cam.c();
+        int64_t drawn = 0;
+        check(lio_overlay_draw_undistorted(h_, ud.handle(), &c, Rt.data(), raw, pitch ? pitch : (int64_t)ud.channels() * ud.rawWidth(),
+                                           out, out_pitch ? out_pitch : (int64_t)ud.channels() * ud.width(),
+                                           owner_image(cam, owner_opt), &drawn),
+              "PointOverlay::drawUndistorted");
+        return drawn;
+    }
+    // device ms of the last draw: upload, fill, stamp, compose, download
+    std::array<double, 5> timing() {
+        std::array<double, 5> ms{};
+        check(lio_overlay_get_timing(h_, ms.data()), "PointOverlay::timing");
+        return ms;
+    }
+
+private:
+    static int32_t* owner_image(const CameraModel& cam, std::vector<int32_t>* owner_opt) {
+        if (!owner_opt) return nullptr;
+        owner_opt->assign((size_t)std::max(cam.width, 0) * (size_t)std::max(cam.height, 0), -1);
+        return owner_opt->data();
+    }
+    lio_overlay* h_ = nullptr;
+};
+
 // The host side of the reference's correct_exposure (post_process/exposure_adaption/correct_exposure:6-70): 256-entry
 // tables from a 256-bin histogram, as lio_gpu.exposure has them.  hist: 256 counts, not all zero.
 using ExposureLut = std::array<uint8_t, 256>;
