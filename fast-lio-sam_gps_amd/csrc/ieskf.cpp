@@ -187,10 +187,12 @@ void boxplus(State& x, const double* d) {
     s2_plus(x.grav, d + 21);
 }
 
-// In-place inverse by LU with partial pivoting (PartialPivLU::inverse()).
-bool lu_inverse(Mat& A, int n) {
-    std::vector<int> piv(n);
-    Mat LU = A;
+// In-place inverse by LU with partial pivoting (PartialPivLU::inverse()) of the n x n matrix A, n <= N
+// (the callers: 6, or dof < N); the work arrays live on the stack.
+bool lu_inverse(double* A, int n) {
+    int piv[N];
+    double LU[N * N], X[N * N], col[N];
+    std::memcpy(LU, A, sizeof(double) * (size_t)n * n);
     for (int k = 0; k < n; ++k) {
         int p = k;
         double best = std::fabs(LU[(size_t)k * n + k]);
@@ -213,8 +215,6 @@ bool lu_inverse(Mat& A, int n) {
         }
     }
     // solve LU X = P I column by column
-    Mat X((size_t)n * n, 0.0);
-    std::vector<double> col(n);
     for (int j = 0; j < n; ++j) {
         for (int i = 0; i < n; ++i) col[i] = (i == j) ? 1.0 : 0.0;
         for (int k = 0; k < n; ++k)
@@ -231,7 +231,7 @@ bool lu_inverse(Mat& A, int n) {
         }
         for (int i = 0; i < n; ++i) X[(size_t)i * n + j] = col[i];
     }
-    A.swap(X);
+    std::memcpy(A, X, sizeof(double) * (size_t)n * n);
     return true;
 }
 
@@ -293,8 +293,8 @@ int update_iterated(State& x, Mat& P, double R, int max_iter, double epsi, const
     using clk = std::chrono::steady_clock;
     const State x_prop = x;
     const Mat P_prop = P;
-    Mat K_x((size_t)N * N, 0.0), Mm(36);
-    double K_h[N], dx_new[N], dxu[N];
+    Mat K_x((size_t)N * N, 0.0), L((size_t)N * N), Pn((size_t)N * N);  // sized once, outside the loop
+    double K_h[N], dx_new[N], dxu[N], Mm[36];
     bool converge = true;
     int t = 0;
     HModel hm;
@@ -355,7 +355,7 @@ int update_iterated(State& x, Mat& P, double R, int max_iter, double epsi, const
                     for (int c = 0; c < 6; ++c) s += H[7 * a + c] * PHt[(size_t)c * dof + b];
                     S[(size_t)a * dof + b] = s / R + (a == b ? 1.0 : 0.0);
                 }
-            if (!lu_inverse(S, dof)) return -4;
+            if (!lu_inverse(S.data(), dof)) return -4;
             for (int r = 0; r < N; ++r) {
                 double kh = 0;
                 double kx[6] = {0, 0, 0, 0, 0, 0};
@@ -383,7 +383,6 @@ int update_iterated(State& x, Mat& P, double R, int max_iter, double epsi, const
             double PR[N * 6];
             for (int r = 0; r < N; ++r)
                 for (int m = 0; m < 6; ++m) PR[r * 6 + m] = P[(size_t)r * N + m] / R;
-            Mm.assign(36, 0.0);
             for (int a = 0; a < 6; ++a)
                 for (int b = 0; b < 6; ++b) {
                     double s = 0;
@@ -426,7 +425,7 @@ int update_iterated(State& x, Mat& P, double R, int max_iter, double epsi, const
         if (converge) ++t;
         if (!t && i == max_iter - 2) converge = true;
         if (t > 1 || i == max_iter - 1) {
-            Mat L = P;
+            L = P;
             for (int idx : kSO3) {
                 const M3 At = transpose(a_matrix(dxu + idx));
                 rows_apply(L, P, N, idx, At.a, 3, N);
@@ -442,7 +441,6 @@ int update_iterated(State& x, Mat& P, double R, int max_iter, double epsi, const
                 cols_apply(L, N, N, kS2, T2, 2);
                 cols_apply(P, N, N, kS2, T2, 2);
             }
-            Mat Pn((size_t)N * N);
             // K_x columns 6..11 stay zero (the block transforms above mix rows only): their terms are
             // exact zeros, skipped
             for (int r = 0; r < N; ++r)

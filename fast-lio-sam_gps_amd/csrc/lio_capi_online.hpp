@@ -58,12 +58,11 @@ struct lio_ctx {
     int64_t* d_nrows = nullptr;
     lio_pose last_pose{};
     lio_pose knn_pose{};  // pose of the last kNN evaluation (Nearest_Points)
-    int* d_far_list = nullptr;  // far-pass queue (cap), its length, and queued lists (cap*5)
+    lio::FarEntry* d_far_q = nullptr;  // far-pass queue (one entry per queued query) and its length
+    int64_t far_cap = 0;
     int* d_far_count = nullptr;
     unsigned* d_done = nullptr;  // plane/reuse block counter (last block publishes)
-    float* d_far_d = nullptr;
-    int* d_far_id = nullptr;
-    float* d_d5 = nullptr;  // per point: 5th neighbour d2 of the last kNN (seeds the next one)
+    float* d_d5 = nullptr;  // per point: 5th neighbour d2 of the last kNN
     float* d_dbg = nullptr;  // scratch of the debug readers (lio_get_knn / _planes / _world, lio_ctx_knn_stats)
     int64_t dbg_cap = 0;
     bool have_eval = false;

@@ -16,7 +16,7 @@ using namespace lio::capi;
 // everything a context owns (a context that lio_ctx_create could only half build included)
 static void ctx_free(lio_ctx& c) {
     lio::dev_free(&c.d_body, &c.d_nn, &c.d_planes, &c.d_sel, &c.d_partials, &c.d_sums, &c.d_rows, &c.d_nrows,
-                  &c.d_far_list, &c.d_far_count, &c.d_far_d, &c.d_far_id, &c.d_done, &c.d_d5, &c.d_dbg, &c.d_raw,
+                  &c.d_far_q, &c.d_far_count, &c.d_done, &c.d_d5, &c.d_dbg, &c.d_raw,
                   &c.d_rec, &c.d_poses, &c.d_kf);
     lio::host_free(&c.h_sums);
     for (hipEvent_t* e : {&c.ev_main.a, &c.ev_main.b, &c.ev_fin.a, &c.ev_fin.b})
@@ -27,18 +27,19 @@ static void ctx_free(lio_ctx& c) {
 }
 
 int lio::capi::ctx_reserve(lio_ctx* c, int64_t n) {
-    // the eight are allocated all or nothing, so d_body stands for all of them (a capacity of 0 leaves it null too)
+    // the five are allocated all or nothing, so d_body stands for all of them (a capacity of 0 leaves it null too)
     if (n > c->cap || !c->d_body) {
         const int64_t cap = std::max<int64_t>(n, c->cap + c->cap / 2);
         c->cap = 0;  // a failed reallocation below leaves no buffer that looks usable
         if (lio::dev_alloc_all({lio::dev_req(c->d_body, cap * 3), lio::dev_req(c->d_nn, cap * 5),
                                 lio::dev_req(c->d_planes, cap), lio::dev_req(c->d_sel, cap + 64),
-                                lio::dev_req(c->d_far_list, cap), lio::dev_req(c->d_far_d, cap * 5),
-                                lio::dev_req(c->d_far_id, cap * 5), lio::dev_req(c->d_d5, cap)}))
+                                lio::dev_req(c->d_d5, cap)}))
             return fail(LIO_ERR_NOMEM, "scan buffers: hipMalloc failed");
         c->cap = cap;
     }
     int rc = grow(&c->d_partials, c->part_cap, (int64_t)lio::match_blocks((int)n) * 32 + 32);
+    if (rc) return rc;
+    rc = grow(&c->d_far_q, c->far_cap, lio::far_entries(n));  // every query may be queued
     if (rc) return rc;
     c->n = n;
     c->body_ext = nullptr;
@@ -130,22 +131,6 @@ static lio::MatchArgs make_args(lio_ctx* c, const lio_pose& pose_in) {
     a.nn_idx = c->d_nn;
     a.nn_d5 = c->d_d5;
     a.seed_scale = c->seed_scale;
-    {
-        const lio_pose pk = filled(c->knn_pose);
-        std::memcpy(&a.pose_knn, &pk, sizeof(lio::PoseArg));
-        // float affine map body -> world of that pose, [R R_LI | R t_LI + t], from the quaternions the
-        // kernels rotate with (never from R / R_LI, which a caller may leave stale)
-        double R[9], RL[9];
-        quat_to_mat(pk.q, R);
-        quat_to_mat(pk.q_LI, RL);
-        for (int r = 0; r < 3; ++r) {
-            for (int k = 0; k < 3; ++k)
-                a.knn_M[4 * r + k] =
-                    (float)(R[3 * r] * RL[k] + R[3 * r + 1] * RL[3 + k] + R[3 * r + 2] * RL[6 + k]);
-            a.knn_M[4 * r + 3] =
-                (float)(R[3 * r] * pk.t_LI[0] + R[3 * r + 1] * pk.t_LI[1] + R[3 * r + 2] * pk.t_LI[2] + pk.t[r]);
-        }
-    }
     a.planes = c->d_planes;
     a.sel = c->d_sel;
     a.partials = c->d_partials;
@@ -156,11 +141,9 @@ static lio::MatchArgs make_args(lio_ctx* c, const lio_pose& pose_in) {
     a.sums_out = c->h_sums_dev;
     a.seq_out = reinterpret_cast<unsigned long long*>(c->h_sums_dev + 32);
     a.seq = 0;
-    a.far_list = c->d_far_list;
+    a.far_q = c->d_far_q;
     a.far_count = c->d_far_count;
     a.done_count = c->d_done;
-    a.far_d = c->d_far_d;
-    a.far_id = c->d_far_id;
     a.range_sq = c->p.knn_range_sq;
     a.plane_thr = c->p.plane_thr;
     a.s_coef = c->p.s_coef;
@@ -202,16 +185,23 @@ static bool read_result(const lio_ctx* c, unsigned long long seq, double* sums) 
     return true;
 }
 
-static int wait_result(lio_ctx* c, unsigned long long seq, double* sums) {
+// The fast path is one cached load per spin.  The stream is queried by elapsed time, not by spin count: first
+// kFirstQuery after the launch (longer than a healthy evaluation at the usual scan sizes, so a result that is
+// about to land never waits behind a runtime call), then every kQueryPeriod.
+static int wait_result(lio_ctx* c, unsigned long long seq, double* sums, std::chrono::steady_clock::time_point launched) {
+    constexpr std::chrono::microseconds kFirstQuery{80}, kQueryPeriod{50};
+    auto next = launched + kFirstQuery;
     for (uint64_t it = 0;; ++it) {
         if (read_result(c, seq, sums)) return LIO_OK;
-        if ((it & 255) == 255) {
-            const hipError_t e = hipStreamQuery(c->map->st);
-            if (e != hipSuccess && e != hipErrorNotReady)
-                return fail(LIO_ERR_HIP, std::string("lio_match: ") + hipGetErrorString(e));
-            if (e == hipSuccess && !read_result(c, seq, sums))
-                return fail(LIO_ERR_HIP, "lio_match: evaluation produced no result");
-        }
+        if ((it & 63) != 63) continue;  // the clock itself every 64 spins
+        const auto now = std::chrono::steady_clock::now();
+        if (now < next) continue;
+        next = now + kQueryPeriod;
+        const hipError_t e = hipStreamQuery(c->map->st);
+        if (e != hipSuccess && e != hipErrorNotReady)
+            return fail(LIO_ERR_HIP, std::string("lio_match: ") + hipGetErrorString(e));
+        if (e == hipSuccess && !read_result(c, seq, sums))
+            return fail(LIO_ERR_HIP, "lio_match: evaluation produced no result");
     }
 }
 
@@ -257,7 +247,7 @@ static int match_impl(lio_ctx* c, const lio_pose* pose_in, int redo_knn, double*
     if (c->timing) HIP_TRY(hipEventRecord(c->ev_main.b, st));
     HIP_TRY(hipGetLastError());
     const auto t1 = std::chrono::steady_clock::now();
-    int rc = wait_result(c, a.seq, sums);
+    int rc = wait_result(c, a.seq, sums, t1);
     if (rc) return rc;
     const auto t2 = std::chrono::steady_clock::now();
     c->last_launch_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
@@ -304,7 +294,7 @@ int lio_ctx_knn_stats(lio_ctx* c, const lio_pose* pose, double* sums, int32_t* s
     hipError_t e2 = hipMemcpyAsync(stats3, c->d_dbg, c->n * 3 * sizeof(int), hipMemcpyDeviceToHost, st);
     hipError_t e3 = hipStreamSynchronize(st);
     if (e2 != hipSuccess || e3 != hipSuccess) return fail(LIO_ERR_HIP, "lio_ctx_knn_stats failed");
-    rc = wait_result(c, a.seq, sums);
+    rc = wait_result(c, a.seq, sums, std::chrono::steady_clock::now());
     if (rc) return rc;
     c->last_pose = *pose;
     c->knn_pose = *pose;

@@ -234,6 +234,16 @@ __device__ __forceinline__ float group_min(float v) {
     }
 }
 
+template <int G, int OFF = 1>
+__device__ __forceinline__ float group_max(float v) {
+    if constexpr (OFF >= G) {
+        return v;
+    } else {
+        v = fmaxf(v, partner_f<OFF>(v));
+        return group_max<G, 2 * OFF>(v);
+    }
+}
+
 // Sort a bitonic (non-decreasing, then non-increasing) list in place.
 template <int K>
 __device__ __forceinline__ void cmpx(uint64_t (&v)[K], int i, int j) {
@@ -633,32 +643,23 @@ __device__ bool group_knn_near(const GridDev& g, float qx, float qy, float qz, i
 }
 
 // Near pass seeded by the query's previous kNN (the second and later kNN
-// evaluations of a scan, map unchanged since): the previous 5th-neighbour
-// distance d5 (at the previous world position w_old) and the query's
-// displacement bound the answer by the triangle inequality — every previous
-// neighbour lies within sqrt(d5) + |w - w_old| of w — so no neighbour has to be
-// re-gathered.  bound = that radius squared (plus margins for float rounding and
-// for w_old from a float affine map),
-// capped at the gate; every lane starts with (bound, kNone) as filler (push
-// keeps every key with d2 <= bound), the 27 cells of the 3x3x3 block are pruned
-// against it and scanned in ONE flat pass, and one merge gives the list.  A
-// list that is not full (impossible for a valid bound, kept as a guard) is
+// evaluations of a scan, map unchanged since): the previous five neighbours are
+// re-gathered by id and B = the largest of their squared distances to the new
+// world point, computed by sqdist3 as the scan computes them.  The map is
+// unchanged, so five distinct live points have d2 <= B and the true 5th key is
+// <= (B, id) < (B, kNone): with (B, kNone) as filler, push keeps every key of
+// the true top-5 and no float margin is needed.  bound = B capped at the gate;
+// every lane starts with (bound, kNone), the 27 cells of the 3x3x3 block are
+// pruned against it and scanned in ONE flat pass, and one merge gives the list.
+// A list that is not full (impossible for a valid bound, kept as a guard) is
 // reset to range fillers and returns -1: the far pass then searches the whole
 // box, the 3x3x3 block included.  Returns 1 when final, 0 when the far pass
 // must search the box outside the block (group_knn_near's false).
-// The seeded pass's bound for query q (float throughout: w_old may come from a float affine map,
-// ~1e-5 m off at 100 m, and every step rounds, so the radius gets an absolute + relative margin and
-// the square a relative one); range_sq when the previous list was not full or q is outside the grid.
-__device__ __forceinline__ float seeded_bound(bool inside, float d5prev, float wox, float woy, float woz, float qx,
-                                             float qy, float qz, float range_sq, float scale) {
+// The seeded pass's bound for a query: b = the group maximum of the previous neighbours' d2 (+inf when
+// the previous list was not full); range_sq when b is beyond it or the query is outside the grid.
+__device__ __forceinline__ float seeded_bound(bool inside, float b, float range_sq, float scale) {
     float bound = range_sq;
-    if (inside && d5prev <= range_sq) {  // the previous list was full
-        const float dx = qx - wox, dy = qy - woy, dz = qz - woz;
-        const float eps = 1e-4f + 1e-6f * ((fabsf(qx) + fabsf(qy)) + fabsf(qz));
-        const float r = (sqrtf(d5prev) + sqrtf((dx * dx + dy * dy) + dz * dz)) + eps;
-        const float b = r * r * (1.0f + 1e-5f);
-        if (b < range_sq) bound = b * scale;  // scale: 1 (< 1 tests the guard)
-    }
+    if (inside && b < range_sq) bound = b * scale;  // scale: 1 (< 1 tests the guard)
     return bound;
 }
 

@@ -7,13 +7,24 @@
 
 namespace lio {
 
+// One queued far-pass query, written by the near pass and fetched by a far block in one round trip: the
+// point index (sign bit: the near pass left the 3x3x3 block unfinished, search it too), the float world
+// point the near pass searched with and its list so far as (d2, id) keys.
+struct alignas(64) FarEntry {
+    int32_t i;
+    float w[3];
+    uint64_t k[5];
+    uint64_t pad;
+};
+static_assert(sizeof(FarEntry) == 64, "FarEntry: one 64-byte line per queued query");
+
 struct MatchArgs {
     PoseArg pose;
     GridDev grid;
     const float* body;        // n*3 feats_down_body
     const float4* map_by_id;  // map points in id order (neighbour coordinates)
     int32_t* nn_idx;          // n*5 Nearest_Points ids
-    float* nn_d5;             // n: 5th neighbour d2 of the last kNN (+inf when fewer than 5; seeds the next one)
+    float* nn_d5;             // n: 5th neighbour d2 of the last kNN (+inf when fewer than 5)
     float4* planes;           // n plane (a,b,c,d) cache
     uint8_t* sel;             // n point_selected_surf
     double* partials;         // nblocks*32
@@ -21,21 +32,17 @@ struct MatchArgs {
     unsigned long long* seq_out;  // written with `seq` after sums_out (host-mapped)
     unsigned long long seq;
     int* dbg;                 // optional n*3 search statistics (diagnostics only)
-    int* far_list;            // n: points queued for the far pass
+    FarEntry* far_q;          // far_entries(n): the queries queued for the far pass, one 64-byte entry each
     int* far_count;           // queue length (reset to 0 by plane_kernel)
     unsigned* done_count;     // blocks of plane/reuse finished (0 between launches; the last block resets it)
-    float* far_d;             // n*5 their near-pass lists
-    int* far_id;
     int n;
     int max_shell;
-    int prior;                // 1: nn_idx holds this scan's previous lists against the unchanged map (seeded near pass)
+    int prior;                // 1: nn_idx holds this scan's previous lists against the unchanged map (seeded near
+                              // pass: their neighbours, re-gathered from map_by_id, give its bound)
     float range_sq;
     float plane_thr;
     double s_coef;
     double s_gate;
-    PoseArg pose_knn;         // pose of the previous kNN evaluation (seeded near pass: w_old)
-    float knn_M[12];          // the same as one float affine map body -> world (row-major 3x4): the seeded
-                              // pass's displacement bound (error covered by a margin)
     float seed_scale;         // seeded bound factor: 1 (lio_ctx_set_seed_scale < 1 forces the not-full guard: tests)
 };
 
@@ -45,6 +52,7 @@ int launch_h_model(const MatchArgs& a, bool redo, hipStream_t st, hipEvent_t* ma
 void launch_debug(const MatchArgs& a, float* world, float* d2, float* abcd_pd2, hipStream_t st);
 void launch_h_rows(const MatchArgs& a, double* rows, int64_t max_rows, int64_t* n_rows, hipStream_t st);
 int match_blocks(int n);
+int64_t far_entries(int64_t n);  // entries the far queue of an n-point scan needs (never fewer than the far grid)
 // batch Nearest_Search: k <= 5 neighbours per query within d2 <= bound (INFINITY: unbounded)
 void launch_map_knn(const GridDev& g, const float* q, int n, float bound, int max_shell, int k, int32_t* idx,
                     float* d2, hipStream_t st);

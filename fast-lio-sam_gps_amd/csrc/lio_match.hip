@@ -3,10 +3,12 @@
 // Per h-evaluation:
 //
 //   ekfom_data.converge == true (redo the kNN):
-//     knn_near_kernel  512 threads = 64 points, 8 lanes per point:
+//     knn_near_kernel  256 threads = 32 points, 8 lanes per point:
 //       body->world (double, stored float) -> exact grid 5-NN over shells 0-1,
 //       cell points scanned lane-strided (coalesced), private top-5 lists
-//       merged by a shuffle butterfly; unresolved points -> far queue
+//       merged by a shuffle butterfly; unresolved points -> far queue (one
+//       64-byte entry each: index, world point, list).  Later kNN evaluations
+//       of a scan: bound = the previous neighbours' exact d2 (re-gathered)
 //     knn_far_kernel   one block per queued point, the rest of its search box
 //     plane_kernel     lane = point: gate (found == 5 && d2[4] <= 5) ->
 //       esti_plane (QR, registers) -> pd2, s-gate -> H row (double) ->
@@ -73,39 +75,38 @@ __global__ void __launch_bounds__(NB) __attribute__((amdgpu_waves_per_eu(8, 8)))
     constexpr int G = kGroup;
     constexpr int QPB = NB / G;  // 64 queries per block
     __shared__ uint32_t s_tab[QPB][72];      // per-group shell-1 slot table
-    __shared__ float s_q[4][QPB];            // per query: world point (and the seeded pass's bound)
+    __shared__ float s_q[3][QPB];            // per query: world point
     __shared__ int s_c[3][QPB];              //            its cell
     const int blk = xcd_block(blockIdx.x, gridDim.x);
     const int sub = threadIdx.x % G;
     const int q = threadIdx.x / G;
     const int i = blk * QPB + q;
     // the per-query transforms once per query, not once per lane of its group: wave 0, lane = query
-    if (threadIdx.x < QPB) {
-        const int iq = blk * QPB + (int)threadIdx.x;
-        if (iq < a.n) {
-            const float bx = a.body[3 * iq], by = a.body[3 * iq + 1], bz = a.body[3 * iq + 2];
-            float wx, wy, wz;
-            body_to_world(ps, bx, by, bz, wx, wy, wz);
-            s_q[0][threadIdx.x] = wx;
-            s_q[1][threadIdx.x] = wy;
-            s_q[2][threadIdx.x] = wz;
-            const int cx = cell_coord(wx, a.grid.ox, a.grid.inv_cell);
-            const int cy = cell_coord(wy, a.grid.oy, a.grid.inv_cell);
-            const int cz = cell_coord(wz, a.grid.oz, a.grid.inv_cell);
-            s_c[0][threadIdx.x] = cx;
-            s_c[1][threadIdx.x] = cy;
-            s_c[2][threadIdx.x] = cz;
-            if constexpr (SEEDED) {
-                // float affine map of the previous kNN pose: w_old within ~1e-5 m, covered by the bound's margin
-                const float* M = a.knn_M;
-                const float wox = ((M[0] * bx + M[1] * by) + M[2] * bz) + M[3];
-                const float woy = ((M[4] * bx + M[5] * by) + M[6] * bz) + M[7];
-                const float woz = ((M[8] * bx + M[9] * by) + M[10] * bz) + M[11];
-                const bool inside = (unsigned)cx < (unsigned)a.grid.nx && (unsigned)cy < (unsigned)a.grid.ny &&
-                                    (unsigned)cz < (unsigned)a.grid.nz;
-                s_q[3][threadIdx.x] = seeded_bound(inside, a.nn_d5[iq], wox, woy, woz, wx, wy, wz, a.range_sq, a.seed_scale);
-            }
-        }
+    const int iq = blk * QPB + (int)threadIdx.x;
+    const bool lead = threadIdx.x < QPB && iq < a.n;
+    float bx, by, bz;  // set and read under `lead` only
+    if (lead) bx = a.body[3 * iq], by = a.body[3 * iq + 1], bz = a.body[3 * iq + 2];
+    // seeded pass: lane sub < 5 fetches the query's previous neighbour `sub` (its own nn_idx row, rewritten only at
+    // the end).  Neither load needs the world point: the ids travel with the body loads, the gathers beside wave
+    // 0's transforms.
+    int pid = -1;
+    float4 pp = make_float4(0.f, 0.f, 0.f, 0.f);
+    if constexpr (SEEDED) {
+        if (sub < 5 && i < a.n) pid = a.nn_idx[5 * (size_t)i + sub];
+        if (pid >= 0) pp = a.map_by_id[pid];
+    }
+    if (lead) {
+        // the body point is first used here: otherwise its conversion to double is hoisted to its load, which then
+        // is waited for before the seeded pass's ids are even requested
+        asm volatile("" : "+v"(bx), "+v"(by), "+v"(bz));
+        float wx, wy, wz;
+        body_to_world(ps, bx, by, bz, wx, wy, wz);
+        s_q[0][threadIdx.x] = wx;
+        s_q[1][threadIdx.x] = wy;
+        s_q[2][threadIdx.x] = wz;
+        s_c[0][threadIdx.x] = cell_coord(wx, a.grid.ox, a.grid.inv_cell);
+        s_c[1][threadIdx.x] = cell_coord(wy, a.grid.oy, a.grid.inv_cell);
+        s_c[2][threadIdx.x] = cell_coord(wz, a.grid.oz, a.grid.inv_cell);
     }
     __syncthreads();
     if (i >= a.n) return;
@@ -114,8 +115,16 @@ __global__ void __launch_bounds__(NB) __attribute__((amdgpu_waves_per_eu(8, 8)))
     tk.init(a.range_sq);
     SearchStats st{0, 0, 0};
     bool done, whole = false;
-    if constexpr (SEEDED) {  // this scan's previous kNN against the same map: the triangle bound (no re-gathers)
-        const int r = group_knn_seeded<5, G, U>(a.grid, s_q[3][q], s_c[0][q], s_c[1][q], s_c[2][q], wx, wy, wz, a.range_sq, sub,
+    if constexpr (SEEDED) {  // this scan's previous kNN against the same map: its neighbours' exact d2 bound this one
+        const int cx = s_c[0][q], cy = s_c[1][q], cz = s_c[2][q];
+        const bool inside = (unsigned)cx < (unsigned)a.grid.nx && (unsigned)cy < (unsigned)a.grid.ny &&
+                            (unsigned)cz < (unsigned)a.grid.nz;
+        // lanes 0-4: the neighbour's d2 as the scan will compute it (+inf: no such neighbour, the list was not
+        // full); lanes 5-7 do not count
+        float d = sub < 5 ? INFINITY : 0.f;
+        if (pid >= 0) d = sqdist3(wx, wy, wz, pp.x, pp.y, pp.z);
+        const float bound = seeded_bound(inside, group_max<G>(d), a.range_sq, a.seed_scale);
+        const int r = group_knn_seeded<5, G, U>(a.grid, bound, cx, cy, cz, wx, wy, wz, a.range_sq, sub,
                                                 tk, s_tab[threadIdx.x / G]);
         done = r > 0;
         whole = r < 0;
@@ -138,13 +147,14 @@ __global__ void __launch_bounds__(NB) __attribute__((amdgpu_waves_per_eu(8, 8)))
     }
     if (far) {
         if (sub == 0) {
-            const int slot = atomicAdd(a.far_count, 1);
-            a.far_list[slot] = whole ? (int)((unsigned)i | 0x80000000u) : i;  // sign bit: search the block too
+            const int slot = atomicAdd(a.far_count, 1);  // < n: a query is queued once
+            FarEntry e;
+            e.i = whole ? (int)((unsigned)i | 0x80000000u) : i;  // sign bit: search the block too
+            e.w[0] = wx, e.w[1] = wy, e.w[2] = wz;
 #pragma unroll
-            for (int j = 0; j < 5; ++j) {
-                a.far_d[5 * (size_t)slot + j] = tk.d(j);
-                a.far_id[5 * (size_t)slot + j] = tk.id(j);
-            }
+            for (int j = 0; j < 5; ++j) e.k[j] = tk.k[j];
+            e.pad = 0;
+            a.far_q[slot] = e;
         }
         return;
     }
@@ -164,27 +174,32 @@ __global__ void __launch_bounds__(NB) __attribute__((amdgpu_waves_per_eu(8, 8)))
 
 // Pass 2: the queued queries, one block each (block_knn_box_flat over the
 // rest of the query's search box).  Fixed grid; every block strides the queue
-// and exits once past its end.
+// and exits once past its end.  A block's first entry is loaded together with
+// the queue length (the queue holds at least gridDim.x entries, far_entries)
+// and used only if the queue reaches it: one round trip before the search.
 template <int NT = kFarBlock>
 __global__ void __launch_bounds__(NT) knn_far_kernel(MatchArgs a) {
-    const PoseArg& ps = a.pose;
     __shared__ uint32_t s_b[NT], s_off[NT + 1], s_w[NT / 64];
     __shared__ uint64_t s_lists[(NT / 64) * 5];
-    const int cnt = *a.far_count;
-    for (int f = blockIdx.x; f < cnt; f += gridDim.x) {
-        const int e = a.far_list[f];
-        const int i = e & 0x7fffffff;
-        float wx, wy, wz;
-        body_to_world(ps, a.body[3 * i], a.body[3 * i + 1], a.body[3 * i + 2], wx, wy, wz);
+    const FarEntry* __restrict__ fq = a.far_q;
+    FarEntry e = fq[blockIdx.x];
+    int cnt = *a.far_count;
+    // both loads above are in flight before either is waited for (without this the compiler sinks the entry's
+    // load behind the branch on the count: two dependent round trips)
+    asm volatile("" : "+s"(cnt), "+v"(e.i), "+v"(e.w[0]), "+v"(e.k[0]), "+v"(e.k[2]), "+v"(e.k[4]));
+    for (int f = blockIdx.x; f < cnt;) {
+        const int i = e.i & 0x7fffffff;
         TopK<5> tk;
 #pragma unroll
-        for (int j = 0; j < 5; ++j) tk.k[j] = knn_key(a.far_d[5 * (size_t)f + j], a.far_id[5 * (size_t)f + j]);
-        block_knn_box_flat<5, NT>(a.grid, wx, wy, wz, s_b, s_off, s_w, s_lists, tk, e < 0);
+        for (int j = 0; j < 5; ++j) tk.k[j] = e.k[j];
+        block_knn_box_flat<5, NT>(a.grid, e.w[0], e.w[1], e.w[2], s_b, s_off, s_w, s_lists, tk, e.i < 0);
         if (threadIdx.x == 0) {
 #pragma unroll
             for (int j = 0; j < 5; ++j) a.nn_idx[5 * (size_t)i + j] = tk.id(j) == kNone ? -1 : tk.id(j);
             a.nn_d5[i] = tk.id(4) == kNone ? INFINITY : tk.d(4);
         }
+        f += gridDim.x;
+        if (f < cnt) e = fq[f];
     }
 }
 
@@ -588,6 +603,10 @@ void launch_map_knn(const GridDev& g, const float* q, int n, float bound, int ma
                     float* d2, hipStream_t st) {
     if (n <= 0) return;
     map_knn_kernel<<<(n + 256 / kGroup - 1) / (256 / kGroup), 256, 0, st>>>(g, q, n, bound, max_shell, k, idx, d2);
+}
+
+int64_t far_entries(int64_t n) {  // a far block loads entry blockIdx.x before it knows the queue's length
+    return std::max<int64_t>(n, kFarBlocks);
 }
 
 int match_blocks(int n) {  // partial slots (plane / reuse kernels): n / 256 bounds both grids
