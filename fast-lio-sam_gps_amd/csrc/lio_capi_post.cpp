@@ -1,6 +1,6 @@
 // lio_capi_post.cpp — the C-ABI (include/lio_gpu.h) of the offline leg's point cloud steps on a lio_filter:
 // statistical outlier removal and the intensity map denoise, Euclidean clusters and DBSCAN, GPS-to-SLAM
-// alignment and georeferencing, RANSAC plane segmentation, k-means.  The handle's create / destroy are in lio_capi_prep.cpp.
+// alignment and georeferencing, RANSAC plane segmentation, k-means, surface normals.  The handle's create / destroy are in lio_capi_prep.cpp.
 #include <algorithm>
 
 #include "lio_capi_util.hpp"
@@ -314,6 +314,41 @@ int lio_kmeans(lio_filter* f, const float* pts, int64_t n, int stride, int K, in
         const int64_t s6[6] = {kr.nf, kr.best, kr.attempt_iters[kr.best], kr.repairs, kr.ec, kr.ed};
         std::memcpy(stats6_opt, s6, sizeof(s6));
     }
+    return LIO_OK;
+}
+
+// ---- surface normals and curvature (lio_normals.hip) ----
+// The arguments are judged before the handle, so a bad call is LIO_ERR_ARG with or without a device.
+int lio_estimate_normals(lio_filter* f, const float* pts, int64_t n, int stride, float radius, int k,
+                         const float* viewpoints_opt, int vp_stride, float* normals_out, float* curvature_opt,
+                         int32_t* counts_opt, int64_t* stats6_opt) {
+    const float r2 = (float)((double)radius * (double)radius);
+    if (n < 0 || n >= (int64_t)1 << 31 || (n > 0 && (!pts || !normals_out)) || stride < 3 || stride > lio::kMaxFields ||
+        !(radius >= 0.f) || !std::isfinite(radius) || (radius > 0.f && (!(r2 > 0.f) || !std::isfinite(r2))) ||
+        (k != 0 && (k < 3 || k > lio::kNmMaxK)) || (k == 0 && !(radius > 0.f)) ||
+        (vp_stride != 0 && (vp_stride < 3 || vp_stride > lio::kMaxFields)))
+        return fail(LIO_ERR_ARG, "lio_estimate_normals: bad arguments");
+    int rc = null_handle(f, "lio_estimate_normals");
+    if (rc) return rc;
+    if (stats6_opt)
+        for (int c = 0; c < 6; ++c) stats6_opt[c] = 0;
+    if (n == 0) return LIO_OK;
+    HIP_TRY(hipSetDevice(f->dev));
+    const int64_t vp_floats = viewpoints_opt ? (vp_stride ? n * vp_stride : 3) : 0;
+    if ((rc = upload_in(f, pts, n * stride))) return rc;
+    rc = lio::normals_reserve(f->nm, n, vp_floats, k > 0);
+    if (rc) return status(rc, "lio_estimate_normals");
+    if (vp_floats)
+        HIP_TRY(hipMemcpyAsync(f->nm.vp, viewpoints_opt, (size_t)vp_floats * sizeof(float), hipMemcpyHostToDevice, f->st));
+    rc = lio::estimate_normals(f->dn, f->nm, f->d_in, n, stride, radius, k, vp_floats ? f->nm.vp : nullptr, vp_stride, f->st);
+    if (rc) return status(rc, "lio_estimate_normals");
+    HIP_TRY(hipMemcpyAsync(normals_out, f->nm.normals, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost, f->st));
+    if (curvature_opt)
+        HIP_TRY(hipMemcpyAsync(curvature_opt, f->nm.curvature, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, f->st));
+    if (counts_opt)
+        HIP_TRY(hipMemcpyAsync(counts_opt, f->nm.counts, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, f->st));
+    HIP_TRY(hipStreamSynchronize(f->st));
+    if (stats6_opt) std::memcpy(stats6_opt, f->nm.h_stats, 6 * sizeof(int64_t));
     return LIO_OK;
 }
 

@@ -133,6 +133,7 @@ int lio_filter_destroy(lio_filter* f) {
         lio::cluster_free(h.cl);
         lio::plane_free(h.pl);
         lio::kmeans_free(h.km);
+        lio::normals_free(h.nm);
         lio::gps_align_free(h.ga);
         lio::project_free(h.pj);
         lio::dev_free(&h.d_in, &h.d_out, &h.d_seg, &h.d_T, &h.d_poses);

@@ -17,6 +17,7 @@
 #include "lio_filter.hpp"
 #include "lio_gpsalign.hpp"
 #include "lio_kmeans.hpp"
+#include "lio_normals.hpp"
 #include "lio_plane.hpp"
 #include "lio_scratch.hpp"
 
@@ -112,6 +113,7 @@ struct lio_filter : lio::capi::Handle {
     lio::ClusterBuf cl;  // lio_euclidean_clusters, lio_dbscan (with dn: the grid, the sorts and the scan)
     lio::PlaneBuf pl;    // lio_segment_plane (with dn: the flags and the scan)
     lio::KMeansBuf km;   // lio_kmeans
+    lio::NormalsBuf nm;  // lio_estimate_normals (with dn: the grid)
     lio::GpsAlignBuf ga; // lio_gps_align, lio_similarity2d_fit, lio_georeference_xy
     lio::ProjectBuf pj;  // lio_project_points, lio_undistort_map
 };

@@ -55,7 +55,7 @@ EXPORTS = [
     "lio_shm_exchange_open", "lio_shm_exchange_allgather", "lio_shm_exchange_close", "lio_shm_exchange_set_timeout",
     "lio_seq_shard_offsets", "lio_seq_shard_merge",
     "lio_sor_filter", "lio_radius_first_seed", "lio_denoise_slam_map", "lio_euclidean_clusters",
-    "lio_segment_plane", "lio_plane_sample_triples", "lio_dbscan", "lio_kmeans",
+    "lio_segment_plane", "lio_plane_sample_triples", "lio_dbscan", "lio_kmeans", "lio_estimate_normals",
     "lio_gps_align", "lio_similarity2d_fit", "lio_georeference_xy",
     "lio_abi_camera_struct_sizes", "lio_project_points", "lio_colorizer_create", "lio_colorizer_destroy",
     "lio_colorizer_set_params", "lio_colorizer_set_cloud", "lio_colorizer_add_frame", "lio_colorizer_get",
@@ -259,6 +259,8 @@ def _declare(L):
         "lio_kmeans": (C.c_int, [vp, fp, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_uint64, fp,
                                  C.POINTER(C.c_int32), fp, dp, C.POINTER(C.c_int64), fp, C.POINTER(C.c_int32),
                                  C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+        "lio_estimate_normals": (C.c_int, [vp, fp, C.c_int64, C.c_int, C.c_float, C.c_int, fp, C.c_int, fp, fp,
+                                           C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
         "lio_segment_plane": (C.c_int, [vp, fp, C.c_int64, C.c_int, C.c_float, C.c_int, C.c_int64, C.c_uint64,
                                         C.POINTER(C.c_int32), fp, C.POINTER(C.c_int64), C.POINTER(C.c_int32),
                                         C.POINTER(C.c_int64), C.POINTER(C.c_uint8), C.POINTER(C.c_int64),

@@ -16,6 +16,8 @@
   core flags and one box per cluster
 * :class:`KMeans`, :func:`cluster_palette` — the projection tool's ``cv::kmeans`` call and its cluster colours
   (post_process/lidar_projection/src/lidar_projection.cpp:82-92, 36-52)
+* :class:`NormalEstimation`, :func:`with_normals` — ``pcl::NormalEstimation`` / Open3D ``estimate_normals``: the
+  normal and curvature fields of the map's PointXYZINormal records, which the reference saves empty
 
 Point records are float rows ``[x, y, z, attr...]`` (3..8 floats); PCL's
 PointXYZI is ``stride = 4``, FAST-LIO's PointXYZINormal-with-time is
@@ -371,6 +373,74 @@ class KMeans(_Handle):
         self.attempt_q, self.attempt_iters, self.stats = attempt_q, attempt_iters, stats
         self.best_attempt, self.n_iter_ = int(stats[1]), int(stats[2])
         return labels
+
+
+class NormalEstimation(_Handle):
+    """``pcl::NormalEstimation`` (``k``: ``setKSearch``; ``radius``: ``setRadiusSearch``) and, with both set,
+    Open3D's hybrid search of ``estimate_normals``, by the contract of ``lio_estimate_normals``: the neighbours are
+    the ``k`` nearest under (float squared distance, index) and / or the points strictly within ``radius``, the
+    covariance comes from integer moments, the normal is the eigenvector of its smallest eigenvalue (cyclic Jacobi
+    in double) and the curvature that eigenvalue over the trace.  It follows PCL's procedure; it is not bit parity
+    with it.  The default is Open3D's and PCL's customary 20 neighbours.
+    After :meth:`compute`: ``curvature`` (n float32), ``counts`` (n: the neighbours used, the point itself
+    included) and ``stats`` = finite points, points with a normal, finite points with fewer than 3 neighbours,
+    degenerate points, the largest neighbourhood, the sum of all.  A point without a normal has NaN."""
+
+    def __init__(self, k: int = 20, radius: float = 0.0, device: int = 0):
+        super().__init__(device)
+        self.k = int(k)
+        self.radius = float(radius)
+        self.curvature = np.zeros(0, np.float32)
+        self.counts = np.zeros(0, np.int32)
+        self.stats = np.zeros(6, np.int64)
+
+    def compute(self, pts: np.ndarray, viewpoint=None) -> np.ndarray:
+        """The normals (n x 3 float32).  ``viewpoint``: ``(3,)`` turns every normal towards that point, ``(n, 3)``
+        each towards its own (the pose that saw the point); ``None``: the sign that makes ``n_z`` (then ``n_y``,
+        then ``n_x``) positive."""
+        pts2 = _rows(pts)
+        n = len(pts2)
+        vp, vp_stride = None, 0
+        if viewpoint is not None:
+            vp = np.ascontiguousarray(viewpoint, dtype=np.float32)
+            if vp.shape == (n, 3) and vp.ndim == 2:
+                vp_stride = 3
+            elif vp.shape != (3,):
+                raise ValueError("viewpoint must be (3,) or (n, 3)")
+        normals = np.full((n, 3), np.nan, np.float32)
+        curvature = np.full(n, np.nan, np.float32)
+        counts = np.zeros(n, np.int32)
+        stats = np.zeros(6, np.int64)
+        check(lib().lio_estimate_normals(self._h, _fp(pts2), n, pts2.shape[1], self.radius, self.k,
+                                         _fp(vp) if vp is not None else None, vp_stride, _fp(normals), _fp(curvature),
+                                         counts.ctypes.data_as(C.POINTER(C.c_int32)),
+                                         stats.ctypes.data_as(C.POINTER(C.c_int64))))
+        self.curvature, self.counts, self.stats = curvature, counts, stats
+        return normals
+
+
+# the float fields of FAST-LIO's PointXYZINormal, the rows of :func:`with_normals`
+POINT_XYZI_NORMAL_FIELDS = ("x", "y", "z", "intensity", "normal_x", "normal_y", "normal_z", "curvature")
+
+
+def with_normals(pts, normals, curvature) -> np.ndarray:
+    """n x 8 float32 rows ``x y z intensity normal_x normal_y normal_z curvature`` — FAST-LIO's PointXYZINormal,
+    which ``lio_gpu.formats.write_pcd_binary(path, rows, POINT_XYZI_NORMAL_FIELDS)`` (``lio_pcd_write_binary``)
+    saves under those names — from ``pts`` (n x 3: intensity 0; n x 4 or wider: column 3), the normals (n x 3) and
+    the curvature (n).  Host only."""
+    pts2 = _rows(pts)
+    n = len(pts2)
+    nrm = np.asarray(normals, np.float32).reshape(-1, 3)
+    cur = np.asarray(curvature, np.float32).reshape(-1)
+    if len(nrm) != n or len(cur) != n:
+        raise ValueError("with_normals: one normal and one curvature per point")
+    out = np.zeros((n, 8), np.float32)
+    out[:, :3] = pts2[:, :3]
+    if pts2.shape[1] > 3:
+        out[:, 3] = pts2[:, 3]
+    out[:, 4:7] = nrm
+    out[:, 7] = cur
+    return out
 
 
 # the ten B, G, R colours of the projection tool's overlay (lidar_projection.cpp:38-49)

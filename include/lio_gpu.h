@@ -678,6 +678,44 @@ int lio_kmeans(lio_filter* f, const float* pts, int64_t n, int stride, int K, in
                int64_t* counts_opt, float* aabb6_opt, int32_t* seeds_opt,
                uint64_t* attempt_q_opt, int32_t* attempt_iters_opt, int64_t* stats6_opt);
 
+/* Surface normals and curvature per point: pcl::NormalEstimation (setKSearch / setRadiusSearch) [U] and Open3D's
+ * estimate_normals with its hybrid search [U], PCL's procedure followed step by step and restated as a contract
+ * of this library, checked exactly against a numpy restatement; it is not bit parity with PCL, whose float
+ * covariance and eigen33 are not pinned here.  pts is n x stride floats (x, y, z first; stride 3..8),
+ * 0 <= n < 2^31; radius 0 or finite and > 0; k 0 or 3..255; not both 0.  No float contraction anywhere.
+ *   neighbours  d2(i, j) = float ((dx*dx + dy*dy) + dz*dz).  For a finite point i the candidates are the finite
+ *               points j, j = i included; with radius > 0 those with d2 < r2, r2 = (float)((double)radius *
+ *               radius): THE TEST IS STRICT (PCL's rule).  With k > 0 and more than k candidates N_i is the k
+ *               smallest under (d2, THEN INDEX j).  k alone is setKSearch, radius alone setRadiusSearch, both
+ *               Open3D's hybrid.  m_i = |N_i|.  A non-finite point is nobody's neighbour: NaN outputs, count 0.
+ *               m_i < 3: NaN outputs, the count still reported.
+ *   moments     integer sums, independent of the order.  B_i = r2 when radius > 0, else the largest d2 in N_i;
+ *               (mant, e) = frexp((double)B_i), h = ceil(e / 2), s = 2^(15 - h); per neighbour o = p_j - p_i in
+ *               float, q_a = (int64) rint((double)o_a s) (|q_a| <= 2^15); S_a = sum q_a, S_ab = sum q_a q_b in
+ *               int64; M_ab = (double)S_ab - ((double)S_a (double)S_b) / (double)m; T = (M_00 + M_11) + M_22.
+ *               B_i = 0, or T > 0 false: the point is DEGENERATE, NaN outputs.
+ *   eigenvector IEEE double, + - * / sqrt only: cyclic Jacobi.  A = M, V = I, at most 10 sweeps; before each
+ *               sweep stop when A_01, A_02 and A_12 are all exactly 0.  A sweep visits (p, q) = (0, 1), (0, 2),
+ *               (1, 2), r the third index, a pair with A_pq = 0 skipped: theta = (A_qq - A_pp) / (2 A_pq);
+ *               t = 1 / (|theta| + sqrt(theta theta + 1)), negated when theta < 0; c = 1 / sqrt(t t + 1);
+ *               s = t c; A_pp -= t A_pq; A_qq += t A_pq; A_pq = 0; (A_rp, A_rq) <- (c A_rp - s A_rq,
+ *               s A_rp + c A_rq); every row of V likewise.  lambda = the diagonal; the column of V of the
+ *               smallest lambda, THE LOWEST INDEX AMONG EQUALS, is the normal; curvature = |lambda| / T.
+ *   orientation with a viewpoint v: s = ((v_x - x) n_x + (v_y - y) n_y) + (v_z - z) n_z in double, the normal
+ *               flipped when s < 0 (a NaN s flips nothing).  viewpoints_opt: vp_stride 0 = one viewpoint of 3
+ *               floats for the whole cloud, vp_stride 3..8 = one row per point (a SLAM map needs the pose that
+ *               saw each point).  NULL: flipped when n_z < 0, or n_z = 0 and n_y < 0, or n_z = n_y = 0 and
+ *               n_x < 0.
+ * normals_out (n x 3 floats, rounded from double); may be NULL, each of them: curvature_opt (n floats), counts_opt
+ * (n: m_i), stats6_opt = finite points, points with a normal, finite points with m < 3, degenerate points, the
+ * largest m, the sum of m.
+ * LIO_ERR_ARG before any device work, with or without a device: every range above, a radius > 0 whose r2 is 0
+ * or infinite, vp_stride not 0 or 3..8, NULL pts / normals_out with n > 0; nothing is written.  Repeated calls and any scheduling of the device give
+ * identical bits; a repeated call of one size allocates nothing (lio_alloc_count).                             */
+int lio_estimate_normals(lio_filter* f, const float* pts, int64_t n, int stride, float radius, int k,
+                         const float* viewpoints_opt, int vp_stride,
+                         float* normals_out, float* curvature_opt, int32_t* counts_opt, int64_t* stats6_opt);
+
 /* ------------------------------- GPS-to-SLAM trajectory alignment and map georeferencing (offline GPS leg) */
 /* Layout of lio_gps_align's result (doubles).  Pairs are (x, y); a rotation is (c, s) for [[c, -s], [s, c]]. */
 #define LIO_GPSALIGN_ITERATIONS 0  /* iterations run                                                          */

@@ -1301,6 +1301,57 @@ private:
     int64_t stats_[6] = {0, 0, 0, 0, 0, 0};
 };
 
+struct Normal {  // pcl::Normal's float fields without the padding
+    float normal_x, normal_y, normal_z, curvature;
+};
+
+// pcl::NormalEstimation<PointT, Normal>: setInputCloud / setKSearch / setRadiusSearch / setViewPoint / compute, by
+// the contract of lio_estimate_normals (lio_gpu.h): the k nearest under (distance, index), or the points strictly
+// within the radius, or — both set, which PCL refuses — Open3D's hybrid search; integer moments, a Jacobi
+// eigenvector in double, the normal turned towards the viewpoint.  The defaults are PCL's: k 0 and radius 0
+// (compute then throws the library's argument error) and the viewpoint (0, 0, 0).  setViewPoints gives one
+// viewpoint per point (the pose that saw it), useNoViewPoint the sign rule that needs none.
+template <typename PointT>
+class NormalEstimation {
+public:
+    explicit NormalEstimation(FilterGPU& f) : f_(f) {}
+    void setInputCloud(const std::vector<PointT>* cloud) { in_ = cloud; }
+    void setKSearch(int k) { k_ = k; }
+    void setRadiusSearch(double radius) { radius_ = radius; }
+    void setViewPoint(float vx, float vy, float vz) { vp_ = {vx, vy, vz}, vp_mode_ = 1; }
+    void setViewPoints(const std::vector<std::array<float, 3>>& viewpoints) { vps_ = viewpoints, vp_mode_ = 2; }
+    void useNoViewPoint() { vp_mode_ = 0; }
+    void compute(std::vector<Normal>& out) {
+        if (!in_) throw Error(LIO_ERR_ARG, "NormalEstimation: no input cloud");
+        const int64_t n = (int64_t)in_->size();
+        if (vp_mode_ == 2 && (int64_t)vps_.size() != n) throw Error(LIO_ERR_ARG, "NormalEstimation: one viewpoint per point");
+        std::vector<float> nrm(3 * (size_t)n + 3), curv((size_t)n + 1);
+        counts_.assign((size_t)n, 0);
+        const float* vp = vp_mode_ == 0 ? nullptr : vp_mode_ == 1 ? vp_.data() : n ? vps_[0].data() : vp_.data();
+        check(lio_estimate_normals(f_.handle(), reinterpret_cast<const float*>(in_->data()), n, float_stride<PointT>(),
+                                   (float)radius_, k_, vp, vp_mode_ == 2 ? 3 : 0, nrm.data(), curv.data(), counts_.data(),
+                                   stats_),
+              "NormalEstimation::compute");
+        out.resize((size_t)n);
+        for (size_t i = 0; i < (size_t)n; ++i) out[i] = {nrm[3 * i], nrm[3 * i + 1], nrm[3 * i + 2], curv[i]};
+    }
+    // of the last compute(): the neighbours of each point; finite points, points with a normal, finite points with
+    // fewer than 3 neighbours, degenerate points, the largest neighbourhood, the sum of all
+    const std::vector<int32_t>& counts() const { return counts_; }
+    const int64_t* stats() const { return stats_; }
+
+private:
+    FilterGPU& f_;
+    const std::vector<PointT>* in_ = nullptr;
+    int k_ = 0;  // PCL's defaults
+    double radius_ = 0.0;
+    int vp_mode_ = 1;
+    std::array<float, 3> vp_ = {0.f, 0.f, 0.f};
+    std::vector<std::array<float, 3>> vps_;
+    std::vector<int32_t> counts_;
+    int64_t stats_[6] = {0, 0, 0, 0, 0, 0};
+};
+
 struct DenoiseConfig {  // fast_lio_sam.h:123-129, defaults of fast_lio_sam.cpp:89-96 (config.yaml:32-42 sets 0.1, 200, 0.2)
     bool denoise_en = false;
     float seed_thres = 2800.0;
